@@ -23,9 +23,13 @@ one generation is ~3 ms and too small to split over 8 GPUs.
 
 The JSON line also carries the roofline of the dominant kernel (the fused
 cross-term GEMM + exp2 + sum, mvn_x3_kernel) timed with HIP events recorded
-by libabcgpu on the launch stream around each launch, and a CPU baseline: the
-numpy oracle (oracle/) timed on a bounded sample of the same generation on
-this host.
+by libabcgpu on the launch stream around each launch.  With `--full` it also
+carries a CPU baseline: the numpy oracle (oracle/) timed on a bounded sample
+of the same generation on this host, after the timed steps; a plain run
+leaves `cpu_baseline` null.  `--dump-outputs DIR` writes the last timed
+generation's results as DIR/<name>.npy (dump_outputs); the sampler's seed is
+fixed, so the same arguments give the same inputs and, from the same build,
+the same arrays.
 """
 import argparse
 import json
@@ -58,6 +62,15 @@ def parse():
                     help="worker processes of the CPU baseline (the box's CPU "
                          "share per GPU is 16)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline (the numpy oracle on "
+                         "--cpu-cores worker processes) after the timed steps; a "
+                         "plain run prints the line with cpu_baseline null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one produced "
+                         "(population, weights, distances, summary statistics, "
+                         "epsilons, the next transition's covariance) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--collectives", default="torch", choices=["torch", "abc"],
                     help="abc: the sampler's all-gathers through libabcgpu's RCCL "
                          "wrappers (abc_comm_*) instead of torch.distributed")
@@ -333,6 +346,43 @@ def measured_traffic(args, n_pop, kernel):
     return None, None
 
 
+DUMP_MAX_ROWS = 1 << 18    # per-particle arrays above this are row-sampled
+
+
+def dump_outputs(out_dir, abc, tr, gens):
+    """What the last timed generation handed to its caller, as float64
+    DIR/<name>.npy: the accepted population (theta, weights, distances,
+    summary statistics, in global candidate order), the epsilon of every timed
+    generation and the one set for the next, the simulation counts, and the
+    covariance of the transition fitted on that population.  Per-particle
+    arrays of more than DUMP_MAX_ROWS rows are cut to the same fixed, seeded,
+    sorted row sample (`rows`), which keeps the dump below 64 MB at the default
+    population (2 x 21 MB for theta and sum_stats, 3 x 2 MB for the rest)."""
+    import torch
+    hist = abc.history
+    t = hist.max_t
+    cols = hist.get_population_device(t)
+    if cols is None:
+        raise RuntimeError("the last generation's population is not on the device")
+    n = len(cols)
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(20251016).choice(
+            n, DUMP_MAX_ROWS, replace=False))
+    else:
+        rows = np.arange(n)
+    idx = torch.from_numpy(rows).to(cols.theta.device)
+    arrays = {name: getattr(cols, name).index_select(0, idx).double().cpu().numpy()
+              for name in ("theta", "weights", "distances", "sum_stats")}
+    arrays["rows"] = rows.astype(np.float64)
+    arrays["eps"] = np.array([g["eps"] for g in gens], dtype=np.float64)
+    arrays["eps_next"] = np.array([abc.eps(t + 1)], dtype=np.float64)
+    arrays["n_sim"] = np.array([g["n_sim"] for g in gens], dtype=np.float64)
+    arrays["transition_cov"] = np.asarray(tr.cov, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -460,8 +510,10 @@ def main():
         # every rank is done with the GPU; rank 0 alone times the host leg
         torch.distributed.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, abc, tr, gens)
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             hist = abc.history
             df, w = hist.get_distribution(0, hist.max_t)
             cores = max(1, min(args.cpu_cores, os.cpu_count() or 1))

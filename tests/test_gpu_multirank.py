@@ -88,13 +88,13 @@ def test_sharded_adaptive_population_size(tmp_path):
 
 
 def test_bench_spawned_ranks():
-    """`python bench.py --gpus 2` with no WORLD_SIZE: bench.py starts its two
+    """`python bench.py --gpus 2 --full` with no WORLD_SIZE: bench.py starts its two
     rank processes itself; rank 0 prints one line with n_gpus = 2 and a CPU
     baseline (timed after the ranks left the GPU)."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--dist-backend", "gloo", "--pop", "20000", "--steps", "2",
+                        "--full", "--dist-backend", "gloo", "--pop", "20000", "--steps", "2",
                         "--warmup", "1", "--cpu-baseline-seconds", "2",
                         "--cpu-cores", "2"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
