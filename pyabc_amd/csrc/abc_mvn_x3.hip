@@ -343,14 +343,138 @@ __device__ __forceinline__ f32x16 mfma32(const half8& a, const half8& b, const f
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
+// The KB fragments of one tile (fragments frag .. frag + KB - 1 of `image`,
+// frag the same in every lane), loaded as scalar base + 32-bit lane offset +
+// immediate so that the addresses stay in SGPRs.  The two empty asm statements
+// (they emit no instruction) keep the compiler from re-associating the sum:
+// otherwise base + lane becomes one 64-bit VGPR address per tile, hoisted out
+// of the loops, and the kernel no longer fits two waves per SIMD.  One base
+// serves 4 fragments (immediates 0 .. 3072; the compiler folds no negative
+// immediate into this address form).  The opaque scalar is the offset, not
+// the pointer: a pointer that comes out of an asm statement is a generic one
+// and its loads become flat loads, which count in lgkmcnt too.
+template <int KB>
+__device__ __forceinline__ void ld_tile(half8 (&a)[KB], const half8* __restrict__ image,
+                                        int64_t frag, uint32_t& lane_bytes) {
+  static_assert(sizeof(half8) * 64 == 1024, "fragment bytes");
+#pragma unroll
+  for (int g = 0; g < (KB + 3) / 4; ++g) {
+    int64_t off = frag * 1024 + g * 4096;
+    asm volatile("" : "+s"(off));
+#pragma unroll
+    for (int kb = 4 * g; kb < KB && kb < 4 * g + 4; ++kb) {
+      asm volatile("" : "+v"(lane_bytes));
+      a[kb] = *reinterpret_cast<const half8*>(reinterpret_cast<const char*>(image) + off +
+                                              lane_bytes + (kb - 4 * g) * 1024);
+    }
+  }
+}
+
+// ---- pass 2's instruction stream ---------------------------------------------
+// A unit is one 32x32 tile pair: KB MFMAs, then 16 exp2 and the 16 adds of a
+// fixed summation tree.  The kernel is bound by vector issue (an MFMA holds it
+// for 8 cycles, v_exp_f32 8, v_add_f32 4: 232 a unit at KB = 5 against 160 of
+// MFMA pipe), so the stream is laid out by hand, one sched_barrier per
+// instruction: the compiler's own placement bunched the exp2 behind one MFMA,
+// left adds directly behind the exp2 they read and padded the MFMA -> exp2
+// hazard with s_nop.  Under the chain of unit u run
+//   gap 0 (behind MFMA 0)  the last six adds of unit u-2 (its tail)
+//   gaps 1 .. KB-1         the 16 exp2 of unit u-1, four a gap at KB = 5, and
+//                          the adds that are ready, none directly behind an
+//                          exp2 it reads
+// so the first exp2 reads an accumulator whose last MFMA issued more than two
+// gaps before (no hazard padding), and every gap carries 32 .. 56 issue cycles.
+// The tree is expsum's: e[i] += e[i + w] for w = 8, 4, 2, 1.
+struct X3Tail { float e3, e11, e7, e15, b1, c0; };
+
+#define X3_PIN() __builtin_amdgcn_sched_barrier(0)
+
+// finishes a unit's sum and adds it to its candidate slot
+__device__ __forceinline__ void x3_tail_ops(const X3Tail& tl, float& ls) {
+  const float a3 = tl.e3 + tl.e11; X3_PIN();
+  const float a7 = tl.e7 + tl.e15; X3_PIN();
+  const float b3 = a3 + a7; X3_PIN();
+  const float c1 = tl.b1 + b3; X3_PIN();
+  const float dd = tl.c0 + c1; X3_PIN();
+  ls += dd; X3_PIN();
+}
+
+// chain of (a, b) -> returned accumulator; beside it the tail `tl` (into
+// ls_tl), then the exp2 and first adds of accumulator v, whose tail is left in tl
+template <int KB>
+__device__ __forceinline__ f32x16 x3_unit(const half8 (&a)[KB], const half8 (&b)[KB],
+                                          const f32x16& v, X3Tail& tl, float& ls_tl) {
+  static_assert(KB >= 2, "gap 0 carries the tail, the exp2 need a later gap");
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
+                         0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // gap of exp2 quad q (four quads over gaps 1 .. KB-1)
+  auto gap = [](int q) { return 1 + q * (KB - 1) / 4; };
+#define X3_E(i) const float e##i = __builtin_amdgcn_exp2f(v[i]); X3_PIN()
+#define X3_A(r, x, y) const float r = x + y; X3_PIN()
+  f32x16 acc = mfma32(a[0], b[0], zero16);
+  X3_PIN();
+  x3_tail_ops(tl, ls_tl);
+  float a0_ = 0.f, a2_ = 0.f, a1_ = 0.f, b0_ = 0.f, e4_ = 0.f, e12_ = 0.f, e6_ = 0.f,
+        e14_ = 0.f, e5_ = 0.f, e13_ = 0.f;
+#pragma unroll
+  for (int kb = 1; kb < KB; ++kb) {
+    acc = mfma32(a[kb], b[kb], acc);
+    X3_PIN();
+    if (gap(0) == kb) {
+      X3_E(0); X3_E(8); X3_E(4); X3_E(12);
+      X3_A(a0, e0, e8);
+      a0_ = a0; e4_ = e4; e12_ = e12;
+    }
+    if (gap(1) == kb) {
+      X3_E(2);
+      X3_A(a4, e4_, e12_);
+      X3_E(10);
+      X3_A(b0, a0_, a4);
+      X3_E(6); X3_E(14);
+      X3_A(a2, e2, e10);
+      b0_ = b0; a2_ = a2; e6_ = e6; e14_ = e14;
+    }
+    if (gap(2) == kb) {
+      X3_E(1);
+      X3_A(a6, e6_, e14_);
+      X3_E(9);
+      X3_A(b2, a2_, a6);
+      X3_E(5);
+      X3_A(c0, b0_, b2);
+      X3_E(13);
+      X3_A(a1, e1, e9);
+      tl.c0 = c0; a1_ = a1; e5_ = e5; e13_ = e13;
+    }
+    if (gap(3) == kb) {
+      X3_E(3);
+      X3_A(a5, e5_, e13_);
+      X3_E(11);
+      X3_A(b1, a1_, a5);
+      X3_E(7); X3_E(15);
+      tl.e3 = e3; tl.e11 = e11; tl.e7 = e7; tl.e15 = e15; tl.b1 = b1;
+    }
+  }
+#undef X3_E
+#undef X3_A
+  return acc;
+}
+
 // one wave's work: candidate tiles ct0 .. ct0 + CT - 1 against population
 // chunk `chunk`
 template <int KB, int CT, bool PASS1>
 __device__ __forceinline__ void x3_wave(
     const half8* __restrict__ A, const half8* __restrict__ Bi, int64_t MT,
-    int64_t NT, int chunk, int64_t tiles_per_chunk, int64_t ct0, int koff, int kb0,
+    int64_t NT, int chunk, int64_t tiles_per_chunk, int64_t ct0_lanes, int koff, int kb0,
     double* __restrict__ part_o, double* __restrict__ part_l, int64_t Mpad) {
   const int lane = threadIdx.x & 63;
+  uint32_t lane_bytes = (uint32_t)lane * (uint32_t)sizeof(half8);
+  // ct0 comes from the wave's number, the same in all 64 lanes: as a scalar
+  // it keeps the tile indices, the fragment addresses and the output rows in
+  // SGPRs (some 30 VGPRs, which the unit stream below needs to stay at two
+  // waves per SIMD, and the address arithmetic off the vector issue port)
+  const int64_t ct0 =
+      (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(ct0_lanes >> 32)) << 32) |
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)ct0_lanes));
   // which lanes / instruction / element of the B fragments hold the offset slot
   const bool off_lane = (lane >> 5) == ((koff >> 3) & 1);
   const int off_kb = koff >> 4, off_j = koff & 7;
@@ -359,15 +483,15 @@ __device__ __forceinline__ void x3_wave(
 #pragma unroll
   for (int c = 0; c < CT; ++c) {
     const int64_t ct = ct0 + c < MT ? ct0 + c : MT - 1;  // clamp: dup work, never stored
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) b[c][kb] = Bi[(ct * KB + kb) * 64 + lane];
+    ld_tile<KB>(b[c], Bi, ct * KB, lane_bytes);
   }
   const int64_t t_begin = (int64_t)chunk * tiles_per_chunk;
   const int64_t t_end = t_begin + tiles_per_chunk < NT ? t_begin + tiles_per_chunk : NT;
   const half8* __restrict__ Al = A + lane;
-  // prefetches run up to 7 tiles past the chunk end (t_end <= NT); the image
-  // carries X3_PAD = 8 pad tiles, so no clamp is needed (pad data is loaded,
-  // never used).  A chunk starting at or past NT (small N) loads nothing.
+  // prefetches run up to 7 tiles past the chunk end (t_end <= NT) in pass 1
+  // and 2 tiles past it in pass 2; the image carries X3_PAD = 8 pad tiles, so
+  // no clamp is needed (pad data is loaded; what pass 2 computes from it is
+  // dropped).  A chunk starting at or past NT (small N) loads nothing.
   static_assert(X3_PAD >= 7, "pad must cover the prefetch distance");
   auto tile = [&](int64_t t) { return t * KB; };
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
@@ -420,70 +544,96 @@ __device__ __forceinline__ void x3_wave(
   }
 
   // ---- pass 2: full limb-split GEMM, exp2, sums.  Two register buffers of
-  // population fragments (prefetch distance 2).  Work runs as a stream of
-  // (tile, c) units: the MFMA chain of unit u is issued next to the
-  // exp2/sum of unit u-1, so one wave keeps the MFMA and VALU pipes busy.
+  // population fragments (prefetch distance 2 tiles).  The chunk runs as ONE
+  // stream of (tile, c) units (x3_unit above): beside the MFMA chain of unit u
+  // go the exp2 of unit u-1 and the last adds of unit u-2, across tile
+  // boundaries too; only the chunk's first chain and last sums run alone.
+  // Every candidate slot c sums the same tiles in the same order and the same
+  // tree, so a candidate's bits do not depend on where it sits in the launch
+  // (and so not on the sharding over ranks).
   double l64[CT];
   float ls[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) { l64[c] = 0.0; ls[c] = 0.f; }
-  half8 a0[KB], a1[KB];
+  static_assert(CT >= 2, "a tile's units 0 and 1 are placed apart");
   if (t_begin < t_end) {
+    half8 a0[KB], a1[KB];
+    // all of a0 first, then all of a1: vmcnt counts in order, so the waits
+    // before a chain on one buffer leave the other buffer's KB loads in flight
+    ld_tile<KB>(a0, A, tile(t_begin), lane_bytes);
+    X3_PIN();
+    ld_tile<KB>(a1, A, tile(t_begin + 1), lane_bytes);
+    X3_PIN();
+    auto expsum = [&](const f32x16& v) {
+      float e[16];
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      a0[kb] = Al[(tile(t_begin) + kb) * 64];
-      a1[kb] = Al[(tile(t_begin + 1) + kb) * 64];
-    }
-  }
-  auto chain = [&](const half8 (&a)[KB], int c) {
-    f32x16 r = mfma32(a[0], b[c][0], zero16);
+      for (int i = 0; i < 16; ++i) e[i] = __builtin_amdgcn_exp2f(v[i]);
 #pragma unroll
-    for (int kb = 1; kb < KB; ++kb) r = mfma32(a[kb], b[c][kb], r);
-    return r;
-  };
-  auto expsum = [&](const f32x16& v) {
-    float e[16];
+      for (int w = 8; w >= 1; w >>= 1)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) e[i] = __builtin_amdgcn_exp2f(v[i]);
-#pragma unroll
-    for (int w = 8; w >= 1; w >>= 1)
-#pragma unroll
-      for (int i = 0; i < w; ++i) e[i] += e[i + w];
-    return e[0];
-  };
-  // one tile: units (t, 0..CT-1); the exp2/sum of unit c - 1 is issued under
-  // the MFMA chain of unit c.  Every candidate slot c sums the same tiles in
-  // the same order, so a candidate's bits do not depend on where it sits in
-  // the launch (and so not on the sharding over ranks).
-  auto do_tile = [&](const half8 (&a)[KB]) {
-    f32x16 prev = chain(a, 0);
-#pragma unroll
-    for (int c = 1; c < CT; ++c) {
-      const f32x16 cur = chain(a, c);
-      ls[c - 1] += expsum(prev);
-      prev = cur;
-    }
-    ls[CT - 1] += expsum(prev);
-  };
-  int nflush = 0;
-  for (int64_t t = t_begin; t < t_end; t += 2) {
-    do_tile(a0);
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) a0[kb] = Al[(tile(t + 2) + kb) * 64];
-    if (t + 1 < t_end) {
-      do_tile(a1);
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) a1[kb] = Al[(tile(t + 3) + kb) * 64];
-    }
+        for (int i = 0; i < w; ++i) e[i] += e[i + w];
+      return e[0];
+    };
     // f32 partial sums over at most 4 tiles (64 terms per lane), then fp64
-    if (++nflush == 2) {
-      nflush = 0;
+    auto flush = [&]() {
 #pragma unroll
       for (int c = 0; c < CT; ++c) { l64[c] += (double)ls[c]; ls[c] = 0.f; }
-    }
-  }
+    };
+    // the stream's state: the accumulator whose exp2 are due, and the tail of
+    // the unit before it (zeros add nothing to their slot)
+    X3Tail tail = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 prev = mfma32(a0[0], b[0][0], zero16);
 #pragma unroll
-  for (int c = 0; c < CT; ++c) l64[c] += (double)ls[c];
+    for (int kb = 1; kb < KB; ++kb) prev = mfma32(a0[kb], b[0][kb], prev);
+    // units 1 .. CT-1 of a tile whose unit 0 is `prev`.  Tiles are grouped in
+    // fours from t_begin and a group's f32 sums go to fp64 when it is complete.
+    // Behind unit 1 the slots hold every tile before this one and nothing of
+    // this one (the tail of the tile's unit 0 runs under unit 2), so that is
+    // where the group before is flushed; at the first group it adds zeros, so
+    // the flush is unconditional wherever a group starts.
+    auto rest_of_tile = [&](const half8 (&a)[KB], bool group_start) {
+      prev = x3_unit<KB>(a, b[1], prev, tail, ls[CT - 1]);
+      if (group_start) flush();
+#pragma unroll
+      for (int c = 2; c < CT; ++c) prev = x3_unit<KB>(a, b[c], prev, tail, ls[c - 2]);
+    };
+    // tiles t (in a0, its unit 0 in `prev`) and t + 1 (in a1).  Each buffer is
+    // reloaded behind the last chain that reads it and before the first chain
+    // on the other buffer (loads run to tile t_end + 1, inside the pad); unit 0
+    // of tile t + 2 is issued unconditionally -- past the chunk's last tile it
+    // multiplies loaded pad (or next-chunk) fragments and its accumulator is
+    // dropped.
+    auto tile_pair = [&](int64_t t, bool group_start) {
+      rest_of_tile(a0, group_start);
+      ld_tile<KB>(a0, A, tile(t + 2), lane_bytes);
+      X3_PIN();
+      prev = x3_unit<KB>(a1, b[0], prev, tail, ls[CT - 2]);
+      rest_of_tile(a1, false);
+      ld_tile<KB>(a1, A, tile(t + 3), lane_bytes);
+      X3_PIN();
+      prev = x3_unit<KB>(a0, b[0], prev, tail, ls[CT - 2]);
+    };
+    // steady state: whole groups of four tiles, no branch in the body
+    const int64_t nt = t_end - t_begin;
+    int64_t t = t_begin;
+    for (int64_t g = nt >> 2; g > 0; --g, t += 4) {
+      tile_pair(t, true);
+      tile_pair(t + 2, false);
+    }
+    if (nt & 2) {
+      tile_pair(t, true);
+      t += 2;
+    }
+    if (nt & 1) {  // the odd last tile, its unit 0 already in `prev`
+      rest_of_tile(a0, (nt & 2) == 0);
+      x3_tail_ops(tail, ls[CT - 2]);
+      ls[CT - 1] += expsum(prev);
+    } else {
+      x3_tail_ops(tail, ls[CT - 1]);
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) l64[c] += (double)ls[c];
+  }
   // lanes l and l ^ 32 hold the same candidate column (same o)
 #pragma unroll
   for (int c = 0; c < CT; ++c) {
@@ -496,6 +646,7 @@ __device__ __forceinline__ void x3_wave(
     }
   }
 }
+#undef X3_PIN
 
 // blocks: (groups of 4 waves x CT candidate tiles) x population chunks; a
 // device-sized launch (count_dev) covers a few groups and strides over the
