@@ -69,7 +69,19 @@ def prior_logpdf(theta, kinds, params):
             elif kind == "laplace":
                 lp += stats.laplace.logpdf(x, p[0], p[1])
             elif kind == "lognorm":
-                lp += np.log(stats.lognorm.pdf(x, p[0], p[1], p[2]))
+                # logpdf, not log(pdf): for a wide s the density next to loc
+                # exceeds the largest double while its log is ~700.  scipy
+                # takes log(s y sqrt(2 pi)) of a product that overflows for
+                # y near the largest double and is rounded for a subnormal
+                # one: there the same density through scipy's normal,
+                # log f(y) = norm.logpdf(log y; 0, s) - log y
+                with np.errstate(all="ignore"):
+                    l = stats.lognorm.logpdf(x, p[0], p[1], p[2])
+                    y = (x - p[1]) / p[2]
+                    edge = (y > 0) & np.isfinite(y) & ((y < 1e-290) | (y > 1e290))
+                    l[edge] = (stats.norm.logpdf(np.log(y[edge]), 0.0, p[0])
+                               - np.log(y[edge]) - np.log(p[2]))
+                lp += l
             elif kind == "gamma":
                 lp += np.log(stats.gamma.pdf(x, p[0], p[1], p[2]))
             elif kind == "beta":
@@ -126,6 +138,112 @@ def propose_mvn(X, w, L, seed, generation, idx0, B, kinds=None, params=None,
         att[pos[ok]] = a + 1
         todo[pos[ok]] = False
     return theta, lp, anc, att
+
+
+def gamma_draws(a, index, base, generation, seed):
+    """Device gamma_draw replayed (pyabc_amd/csrc/abc_candidate.h): one
+    Marsaglia-Tsang gamma(a, 1) draw per candidate, iteration `it` from slot
+    base + it (normal = first Box-Muller value of words 0, 1; accept uniform
+    = word 2); for a < 1 the boost u^(1/a) from word 0 of slot base + 500 and
+    the draw of a + 1.  Returns (draw, margin): margin is the smallest
+    |log u - rhs| over the accept tests the candidate met -- the only
+    decisions that depend on the device's log."""
+    index = np.asarray(index, dtype=np.uint64)
+    n = len(index)
+    a = float(a)
+    boost = np.ones(n)
+    if a < 1.0:
+        r = philox4x32_10(index, base + 500, generation, seed)
+        boost = uniform01(r[:, 0]) ** (1.0 / a)
+        a += 1.0
+    dd = a - 1.0 / 3.0
+    c = 1.0 / np.sqrt(9.0 * dd)
+    out = dd * boost            # the device's value after 480 rejections
+    margin = np.full(n, np.inf)
+    todo = np.ones(n, dtype=bool)
+    for it in range(480):
+        pos = np.nonzero(todo)[0]
+        if len(pos) == 0:
+            break
+        r = philox4x32_10(index[pos], base + it, generation, seed)
+        n0, _ = normal_pairs(r[:, 0], r[:, 1])
+        v = 1.0 + c * n0
+        live = v > 0.0
+        v = np.where(live, v, 1.0)
+        v = v * v * v
+        lu = np.log(uniform01(r[:, 2]))
+        rhs = 0.5 * n0 * n0 + dd - dd * v + dd * np.log(v)
+        margin[pos[live]] = np.minimum(margin[pos[live]], np.abs(lu - rhs)[live])
+        acc = live & (lu < rhs)
+        out[pos[acc]] = dd * v[acc] * boost[pos[acc]]
+        todo[pos[acc]] = False
+    return out, margin
+
+
+def prior_draws(kind, p, index, base, generation, seed):
+    """Device prior_draw1 replayed for one coordinate: (draw, margin) of the
+    candidates `index` from the streams at slot `base` (gamma: base + 1 + it;
+    beta: a second gamma stream at base + 1 + 256 + it).  margin as in
+    gamma_draws (inf for the kinds that make no accept decision)."""
+    index = np.asarray(index, dtype=np.uint64)
+    inf = np.full(len(index), np.inf)
+    if kind == "gamma":
+        x, m = gamma_draws(p[0], index, base + 1, generation, seed)
+        return p[1] + p[2] * x, m
+    if kind == "beta":
+        x, mx = gamma_draws(p[0], index, base + 1, generation, seed)
+        y, my = gamma_draws(p[1], index, base + 1 + 256, generation, seed)
+        return p[2] + p[3] * x / (x + y), np.minimum(mx, my)
+    r = philox4x32_10(index, base, generation, seed)
+    if kind == "norm":
+        n0, _ = normal_pairs(r[:, 0], r[:, 1])
+        return p[0] + p[1] * n0, inf
+    if kind == "uniform":
+        return p[0] + p[1] * uniform53(r[:, 0], r[:, 1]), inf
+    if kind == "expon":
+        return p[0] - p[1] * np.log(uniform01(r[:, 0])), inf
+    if kind == "laplace":
+        u = uniform01(r[:, 0]) - 0.5
+        return p[0] - p[1] * np.copysign(1.0, u) * np.log1p(-2.0 * np.abs(u)), inf
+    if kind == "lognorm":
+        n0, _ = normal_pairs(r[:, 0], r[:, 1])
+        with np.errstate(over="ignore", under="ignore"):
+            return p[1] + p[2] * np.exp(p[0] * n0), inf
+    raise ValueError(kind)
+
+
+def propose_prior(kinds, params, seed, generation, idx0, B, max_attempts=1000):
+    """Device abc_propose with X == nullptr replayed (PROP_PRIOR, the t = 0
+    proposal, smc.py:624-626: theta = prior.rvs()): coordinate k of attempt a
+    from slot a * 65536 + SLOT_PRIOR + 512 k, the whole row re-drawn while
+    the prior density (scipy's, prior_logpdf) is 0.  Returns theta, prior
+    logpdf, attempts (max_attempts + 1: every attempt left the support; theta
+    is then the last one, logpdf -inf) and the smallest accept margin of the
+    row's gamma / beta draws over all its attempts."""
+    params = np.asarray(params, dtype=np.float64)
+    d = len(kinds)
+    idx = np.arange(idx0, idx0 + B, dtype=np.uint64)
+    theta = np.empty((B, d))
+    lp = np.full(B, -np.inf)
+    att = np.full(B, max_attempts + 1, dtype=np.int64)
+    margin = np.full(B, np.inf)
+    todo = np.ones(B, dtype=bool)
+    for a in range(max_attempts):
+        pos = np.nonzero(todo)[0]
+        if len(pos) == 0:
+            break
+        th = np.empty((len(pos), d))
+        for k in range(d):
+            base = a * SLOTS_PER_ATTEMPT + SLOT_PRIOR + 512 * k
+            th[:, k], m = prior_draws(kinds[k], params[k], idx[pos], base, generation, seed)
+            margin[pos] = np.minimum(margin[pos], m)
+        l = prior_logpdf(th, kinds, params)
+        theta[pos] = th
+        ok = l > -np.inf
+        lp[pos[ok]] = l[ok]
+        att[pos[ok]] = a + 1
+        todo[pos[ok]] = False
+    return theta, lp, att, margin
 
 
 def prior_uniforms(index, att, k, generation, seed):

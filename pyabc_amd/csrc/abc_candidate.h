@@ -64,7 +64,9 @@ __device__ __noinline__ double prior_logpdf1(int kind, const double* p, double x
       return 0.0;
     case ABC_PRIOR_NORM: {
       double y = (x - p[0]) / p[1];
-      return -0.5 * y * y - LOG_SQRT_2PI - log(p[1]);
+      // (y y) / 2, not (y / 2) y: -inf exactly where prior_in_support1's and
+      // scipy's y^2 overflows (the same bits wherever it does not)
+      return -0.5 * (y * y) - LOG_SQRT_2PI - log(p[1]);
     }
     case ABC_PRIOR_UNIFORM: {
       double y = (x - p[0]) / p[1];
@@ -81,14 +83,19 @@ __device__ __noinline__ double prior_logpdf1(int kind, const double* p, double x
     case ABC_PRIOR_LOGNORM: {  // s, loc, scale
       double y = (x - p[1]) / p[2];
       if (!(y > 0.0)) return -INFINITY;
-      double ly = log(y) / p[0];
-      return -0.5 * ly * ly - log(p[0] * y) - LOG_SQRT_2PI - log(p[2]);
+      // log(s) + log(y), not log(s y): the product overflows for y near the
+      // largest double and rounds (to 0 for s <= 1/2) for a subnormal y,
+      // where the log density itself is finite
+      const double lg = log(y), ly = lg / p[0];
+      return -0.5 * ly * ly - lg - log(p[0]) - LOG_SQRT_2PI - log(p[2]);
     }
     case ABC_PRIOR_GAMMA: {  // a, loc, scale
       double a = p[0], y = (x - p[1]) / p[2];
       if (y < 0.0) return -INFINITY;
       if (y == 0.0) return a < 1.0 ? INFINITY : (a == 1.0 ? -log(p[2]) : -INFINITY);
-      return (a - 1.0) * log(y) - y - lgamma(a) - log(p[2]);
+      // a == 1: no 0 * log(inf) = NaN at y = inf (scipy's xlogy: -inf there)
+      const double t1 = (a == 1.0) ? 0.0 : (a - 1.0) * log(y);
+      return t1 - y - lgamma(a) - log(p[2]);
     }
     case ABC_PRIOR_BETA: {  // a, b, loc, scale
       double a = p[0], b = p[1], y = (x - p[2]) / p[3];
@@ -105,8 +112,10 @@ __device__ __noinline__ double prior_logpdf1(int kind, const double* p, double x
 }
 
 // Prior density > 0 at x (the re-draw test of smc.py:654-656), decided on
-// the support alone: exactly the x for which prior_logpdf1 is not -inf / NaN
-// (up to overflow of a finite log density), without its transcendentals.
+// the support alone: exactly the x for which prior_logpdf1 is not -inf / NaN,
+// without its transcendentals, for parameters inside the family's domain
+// (support_bounds_wave checks that; tests/test_gpu_priors.py holds the two
+// functions to this).
 __device__ __forceinline__ bool prior_in_support1(int kind, const double* p, double x) {
   switch (kind) {
     case ABC_PRIOR_FLAT:
@@ -319,9 +328,43 @@ __device__ __forceinline__ void support_bounds_wave(int kind, const double* pg, 
     case ABC_PRIOR_HOST: c = p[2]; break;
     default: c = 0.0;
   }
-  if (!prior_in_support1(kind, p, c)) {
-    if (lane == 0) { lo_hi[0] = INFINITY; lo_hi[1] = -INFINITY; }
-    return;
+  // a scale or shape that is not positive and finite is outside the family:
+  // prior_logpdf1 is NaN or -inf everywhere, so nothing is a member (the
+  // tests on y alone would still pass for a NaN shape or an infinite scale)
+  auto pos = [](double v) { return v > 0.0 && v < INFINITY; };
+  bool dom = true;
+  switch (kind) {
+    case ABC_PRIOR_NORM: case ABC_PRIOR_UNIFORM: case ABC_PRIOR_EXPON: case ABC_PRIOR_LAPLACE:
+      dom = pos(p[1]); break;
+    case ABC_PRIOR_LOGNORM: case ABC_PRIOR_GAMMA: dom = pos(p[0]) && pos(p[2]); break;
+    case ABC_PRIOR_BETA: dom = pos(p[0]) && pos(p[1]) && pos(p[3]); break;
+    default: break;
+  }
+  if (!dom || !prior_in_support1(kind, p, c)) {
+    // c is computed in floating point: with a scale below one ulp of loc it
+    // rounds onto loc, which is no member when the density vanishes there
+    // (lognorm, gamma and beta with a > 1) although the doubles above it are
+    // (gamma(2, loc = 1e20, scale = 1)); a beta one ulp wide may have its
+    // only member, an end point, next to c.  So the support is empty only
+    // if the doubles next to a finite c are no members either (c = inf or
+    // NaN: infinite or NaN parameters, no density anywhere).
+    bool found = false;
+    if (dom && fabs(c) < INFINITY) {
+      const uint64_t kc0 = dkey(c);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        double c2 = dval(s ? kc0 - 1 : kc0 + 1);
+        if (c2 == c) c2 = dval(s ? kc0 - 2 : kc0 + 2);   // c = +-0: the other zero
+        if (!found && prior_in_support1(kind, p, c2)) {
+          c = c2;
+          found = true;
+        }
+      }
+    }
+    if (!found) {
+      if (lane == 0) { lo_hi[0] = INFINITY; lo_hi[1] = -INFINITY; }
+      return;
+    }
   }
   // first key in (lo, hi] where pred(key) == up (pred(lo) != up, pred(hi) == up)
   auto turn = [&](uint64_t lo, uint64_t hi, bool up) {

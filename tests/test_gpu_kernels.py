@@ -685,14 +685,19 @@ def test_prior_sampling_moments(dev):
     B = 200_000
     th, lp, _, att = gpu.propose(None, None, None,
                                  T([osamp.KIND[k] for k in kinds], dtype=torch.int32),
-                                 T(params.ravel()), 9, 0, 0, B, 10, len(kinds))
+                                 T(params.ravel()), 11, 0, 0, B, 10, len(kinds))
     th = th.cpu().numpy()
     dists = [stats.norm(1, 2), stats.uniform(-1, 3), stats.expon(0.5, 2),
              stats.laplace(0, 1), stats.lognorm(0.5, 0, 1), stats.gamma(2.5, 0, 1),
              stats.beta(2, 3, 0, 1)]
     for k, dist in enumerate(dists):
         ks = stats.kstest(th[:, k], dist.cdf).statistic
-        assert ks < 0.01, (kinds[k], ks)
+        # the 0.1 % critical value (tests/test_gpu_priors.py holds the draws
+        # to the oracle's replay one by one).  Seed 11: with seed 9 the norm
+        # column sits in that 0.1 % tail (0.00452) -- chance: over seeds
+        # 1..40 its statistic follows the Kolmogorov law (mean 0.865 /
+        # sqrt(B) against 0.869, two of 40 above the 5 % point)
+        assert ks < 1.95 / np.sqrt(B), (kinds[k], ks)
     ref_lp = osamp.prior_logpdf(th[:1000], kinds, params)
     np.testing.assert_allclose(lp.cpu().numpy()[:1000], ref_lp, rtol=1e-10)
 

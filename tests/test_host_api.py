@@ -86,6 +86,92 @@ def test_batched_form_of_priors():
         assert rv.is_discrete
 
 
+def _spec_logpdf(kind_name, par, x):
+    """The density the device evaluates for (kind, [shape.., loc, scale]):
+    scipy's family called with exactly those values, positionally."""
+    n = {"norm": 2, "uniform": 2, "expon": 2, "laplace": 2, "lognorm": 3,
+         "gamma": 3, "beta": 4}[kind_name]
+    return getattr(stats, kind_name).logpdf(x, *par[:n])
+
+
+# (family, positional / keyword / mixed construction, [shape.., loc, scale])
+_FAMILY_FORMS = [
+    ("norm", [((1.5, 2.0), {}), ((), dict(loc=1.5, scale=2.0)), ((1.5,), dict(scale=2.0))],
+     [1.5, 2.0]),
+    ("uniform", [((-1.0, 3.0), {}), ((), dict(loc=-1.0, scale=3.0)),
+                 ((-1.0,), dict(scale=3.0))], [-1.0, 3.0]),
+    ("expon", [((0.5, 2.0), {}), ((), dict(scale=2.0, loc=0.5)), ((0.5,), dict(scale=2.0))],
+     [0.5, 2.0]),
+    ("laplace", [((1.0, 0.5), {}), ((), dict(loc=1.0, scale=0.5)),
+                 ((1.0,), dict(scale=0.5))], [1.0, 0.5]),
+    ("lognorm", [((0.5, 0.0, 2.0), {}), ((), dict(s=0.5, scale=2.0)),
+                 ((0.5,), dict(scale=2.0))], [0.5, 0.0, 2.0]),
+    ("gamma", [((2.0, 1.0, 3.0), {}), ((), dict(a=2.0, loc=1.0, scale=3.0)),
+               ((2.0, 1.0), dict(scale=3))], [2.0, 1.0, 3.0]),
+    ("beta", [((2.0, 3.0, 1.0, 1.0), {}), ((), dict(a=2, b=3, loc=1)),
+              ((2.0,), dict(b=3.0, loc=1.0))], [2.0, 3.0, 1.0, 1.0]),
+]
+
+
+@pytest.mark.parametrize("name,forms,want", _FAMILY_FORMS, ids=[f[0] for f in _FAMILY_FORMS])
+def test_device_family_params_forms(name, forms, want):
+    """RV.device_spec of every device family, built positionally, by keyword
+    and mixed: the family's kind and [shape.., loc, scale] padded to 4, and
+    those values reproduce the RV's own scipy log density (in the support,
+    at its ends and outside)."""
+    from pyabc_amd._native import PRIOR_KINDS as K
+    for args, kwargs in forms:
+        rv = pa.RV(name, *args, **kwargs)
+        kind, par = rv.device_spec()
+        assert kind == K[name] and len(par) == 4
+        assert all(type(v) is float for v in par)
+        assert par == [float(v) for v in want] + [0.0] * (4 - len(want)), (args, kwargs)
+        lo, hi = rv.distribution.support()
+        x = np.concatenate([rv.distribution.ppf([0.01, 0.3, 0.5, 0.9, 0.999]),
+                            [lo, hi, max(lo, -1e300) - 1.0, min(hi, 1e300) + 1.0]])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            np.testing.assert_array_equal(_spec_logpdf(name, par, x),
+                                          rv.distribution.logpdf(x))
+    # defaults: loc 0, scale 1
+    shapes = want[:len(want) - 2]
+    assert pa.RV(name, *shapes).device_spec() == \
+        (K[name], [float(v) for v in shapes] + [0.0, 1.0] + [0.0] * (2 - len(shapes)))
+    d = pa.Distribution(b=pa.RV(name, *forms[0][0]), a=pa.RV("norm", 0, 1))
+    kinds, params = d.device_spec()
+    assert kinds.dtype == np.int32 and list(kinds) == [K["norm"], K[name]]
+    np.testing.assert_array_equal(params.reshape(2, 4)[1], pa.RV(name, *forms[0][0]).device_spec()[1])
+
+
+def test_device_spec_never_a_wrong_family():
+    """Distributions the kernels do not implement -- relatives of the device
+    families, other parametrisations of them -- get the HOST spec (their
+    support interval and a point inside it) or None, never a family's kind
+    with parameters that mean something else."""
+    from pyabc_amd._native import PRIOR_KINDS as K
+    fam = {K[n] for n in ("norm", "uniform", "expon", "laplace", "lognorm", "gamma", "beta")}
+    others = [pa.RV("halfnorm", 0, 1), pa.RV("truncnorm", -1, 2), pa.RV("invgamma", 2.0),
+              pa.RV("gengamma", 2.0, 1.5), pa.RV("loggamma", 2.0), pa.RV("betaprime", 2, 3),
+              pa.RV("loguniform", 1, 10), pa.RV("truncexpon", 3.0), pa.RV("laplace_asymmetric", 2),
+              pa.RV("skewnorm", 1.0), pa.RV("chi2", 3), pa.RV("t", 3, loc=1),
+              pa.RV("powerlognorm", 2.0, 0.5), pa.RV("erlang", 2)]
+    for rv in others:
+        spec = rv.device_spec()
+        assert spec is None or spec[0] == K["host"], rv
+        assert spec is None or spec[0] not in fam
+        if spec is not None:
+            lo, hi, c, _ = spec[1]
+            assert (lo, hi) == tuple(float(v) for v in rv.distribution.support())
+            assert lo <= c <= hi and np.isfinite(c) and rv.distribution.pdf(c) > 0
+    # a family name whose frozen form the mapping cannot read back (an
+    # unknown keyword cannot be frozen by scipy at all)
+    with pytest.raises(TypeError):
+        pa.RV("gamma", 2.0, rate=3.0)
+    with pytest.raises(TypeError):
+        pa.RV("gamma", scale=2.0)       # shape missing
+    # a bounded HOST interval carries its centre
+    assert pa.RV("truncnorm", -1, 2, loc=1).device_spec() == (K["host"], [0.0, 3.0, 1.5, 0.0])
+
+
 def test_model_perturbation_kernel_checks():
     k = pa.ModelPerturbationKernel(3, probability_to_stay=.5)
     assert k.pmf(0, 0) == .5 and k.pmf(1, 0) == .25
