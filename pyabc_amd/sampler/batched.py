@@ -102,6 +102,166 @@ class ColumnarSample:
         return parts[:m]
 
 
+class _PinnedReader:
+    """Device int64 values read on the host with one wait: queue() copies
+    them into a cached pinned buffer (async copies, no concatenation kernel,
+    no allocation) and records an event; wait() returns them.  Work queued
+    after the event (the kept rows' regeneration) runs while the host waits."""
+
+    def __init__(self):
+        self._host = self._event = self._direct = None
+
+    def queue(self, *pieces):
+        torch = gpu.torch
+        self._direct = None
+        if not pieces[0].is_cuda:                  # host tensors (test doubles)
+            self._direct = np.concatenate([t.reshape(-1).numpy() for t in pieces])
+            return
+        sizes = [t.numel() for t in pieces]
+        host = self._host
+        if host is None or host.numel() != sum(sizes):
+            host = self._host = torch.empty(sum(sizes), dtype=torch.int64,
+                                            pin_memory=True)
+            self._event = torch.cuda.Event()
+        off = 0
+        for t, k in zip(pieces, sizes):
+            host[off:off + k].copy_(t.reshape(k), non_blocking=True)
+            off += k
+        # the stream named by the tensor's device: record() with no stream
+        # resolves the current device through torch.cuda.is_available (~40 us)
+        self._event.record(torch.cuda.current_stream(pieces[0].device))
+
+    def wait(self):
+        """The queued values (numpy int64, the caller's own copy)."""
+        if self._direct is not None:
+            return self._direct
+        self._event.synchronize()
+        return self._host.numpy().copy()
+
+
+class _RoundLedger:
+    """Host bookkeeping of one generation's candidate rounds, the same for
+    every loop that runs them: the first-n-accepted cutoff over the ranks
+    (global candidate-index order), evaluations up to the n-th accepted, the
+    rows each rank keeps and records per round, and the cap on recorded rows.
+    Holds no device tensor but the pending cut's position."""
+
+    def __init__(self, n, rank, ws, S, max_recorded, budget_bytes=None):
+        self.n, self.rank, self.ws = n, rank, ws
+        self.n_acc = self.n_eval = self.base = self.rounds = 0
+        self.keeps = []         # per round: accepted rows kept by each rank
+        self.rec_keeps = []     # per round: recorded rows of each rank
+        self.cut = None         # ws > 1: the last round's cutoff, see finish
+        # recorded rows still allowed: the first max_recorded are all that is
+        # used, fewer when the device budget holds fewer rows of S statistics
+        self.rec_left = max_recorded
+        self.records_truncated = False
+        self._budget_bytes = None           # set: the budget is the cap
+        if budget_bytes is not None:
+            budget_rows = budget_bytes // (8 * max(S, 1))
+            if budget_rows < max_recorded:
+                self._budget_bytes = budget_bytes
+            self.rec_left = min(max_recorded, budget_rows)
+
+    @property
+    def need(self):
+        return self.n - self.n_acc
+
+    def settle(self, counts, B, idx, pos, recording):
+        """Book one completed round of B candidates per rank.  counts: the
+        accept count of every rank (host); idx: this rank's accepted
+        positions (device, read only by a pending cut); pos: on one rank the
+        position of the need-th accepted (meaningful when the round completes
+        the sample); recording: whether the round wrote its candidates' rows.
+        Returns (rows this rank keeps, rows this rank records); the latter is
+        None while a multi-rank cut is pending (finish gives it)."""
+        ws = self.ws
+        keep = dd.cutoff(counts, self.need)
+        total_keep = int(keep.sum())
+        # evaluations up to the cutoff (global order); rec_all = recorded
+        # rows of every rank this round (identical on all ranks)
+        rec_all = np.full(ws, B if recording else 0, dtype=np.int64)
+        if self.n_acc + total_keep >= self.n:
+            c_rank = int(np.nonzero(keep)[0][-1])
+            if ws > 1:
+                # the cutoff position travels in the generation's packed
+                # row gather (_assemble), not in a collective of its own
+                self.cut = self._pending_cut(idx, int(keep[c_rank]), c_rank, B)
+                evaluated = 0
+                if recording:
+                    rec_all = None
+            else:
+                evaluated = c_rank * B + pos + 1
+                if recording:
+                    rec_all = self._rows_up_to(c_rank, pos, B)
+        else:
+            evaluated = ws * B
+        if rec_all is not None:
+            rec_all = self._cap_records(rec_all)
+        self.rec_keeps.append(rec_all)
+        self.keeps.append(keep)
+        self.n_acc += total_keep
+        self.n_eval += evaluated
+        self.base += ws * B
+        self.rounds += 1
+        return int(keep[self.rank]), (None if rec_all is None
+                                      else int(rec_all[self.rank]))
+
+    def finish(self, gathered):
+        """Resolve the pending cut once the packed row gather has brought the
+        cut rank's position (gathered[rank]): adds the last round's
+        evaluations up to the n-th accepted (global order) and caps that
+        round's recorded rows like every round's.  Returns the rows this
+        rank's recorded pieces of that round are trimmed to (None: nothing
+        to trim)."""
+        if self.cut is None:
+            return None
+        c_rank, B = self.cut["c_rank"], self.cut["B"]
+        pos = int(gathered[c_rank])
+        self.n_eval += c_rank * B + pos + 1
+        if self.rec_keeps[-1] is not None:
+            return None
+        rec_all = self._cap_records(self._rows_up_to(c_rank, pos, B))
+        self.rec_keeps[-1] = rec_all
+        return int(rec_all[self.rank])
+
+    def _rows_up_to(self, c_rank, pos, B):
+        """Recorded rows per rank of the round cut at c_rank's position pos."""
+        rec_all = np.full(self.ws, B, dtype=np.int64)
+        rec_all[c_rank] = pos + 1
+        rec_all[c_rank + 1:] = 0
+        return rec_all
+
+    def _pending_cut(self, idx, k, c_rank, B):
+        """The completing round of a multi-rank generation: the cut rank's
+        local position of its last (k-th) kept candidate stays on the device
+        (no host read, no collective of its own) and rides in the packed row
+        gather of _assemble; every other rank sends -1."""
+        if self.rank == c_rank:
+            pos = idx[k - 1:k].to(gpu.F64)
+        else:
+            pos = gpu.torch.full((1,), -1.0, dtype=gpu.F64, device=idx.device)
+        return dict(c_rank=c_rank, B=int(B), pos=pos)
+
+    def _cap_records(self, rec_all):
+        """Keep only the first rec_left recorded candidates in global order
+        (round-major, then rank): the round's rows per rank after the cap."""
+        if not np.isfinite(self.rec_left):
+            return rec_all
+        out = np.zeros_like(rec_all)
+        left = int(self.rec_left)
+        for q in range(len(rec_all)):
+            out[q] = min(int(rec_all[q]), left)
+            left -= int(out[q])
+        if left == 0 and out.sum() < rec_all.sum() and self._budget_bytes is not None:
+            if not self.records_truncated:
+                logger.warning("recorded sum stats exceed record_device_budget_bytes "
+                               "(%d); keeping the first rows only", self._budget_bytes)
+            self.records_truncated = True
+        self.rec_left = left
+        return out
+
+
 class BatchedGPUSampler(Sampler):
     """Batched, device-resident sampler (single model, nr_samples_per_param 1).
     Closures outside that (a plain ``simulate_one``, a scalar model, ...) run
@@ -187,6 +347,9 @@ class BatchedGPUSampler(Sampler):
         # line), run once this generation's transition density is queued --
         # the longest kernel, so the host work overlaps it
         self.on_density_queued = None
+        self._reader = _PinnedReader()     # the round's counts, one wait
+        self._pool = (None, 0)             # (_kept_buffers' arena, offset)
+        self._prop = (None, None, None)    # (spec, key, round) of _proposal_round
 
     def _base_seed(self, device):
         if self.seed is None:
@@ -220,36 +383,29 @@ class BatchedGPUSampler(Sampler):
         if fr is not None:
             return self._sample_fused(n, fr, spec, max_eval, record, dev, rank, ws)
 
-        acc_theta, acc_lp, acc_d, acc_x, acc_anc, acc_w = [], [], [], [], [], []
+        S = len(spec.sum_stat_keys)
+        kept = {k: [] for k in self._KEPT}       # kept rows' columns per round
         rec_x = []
+        # no distance decides (calibration): every candidate is kept
+        unfiltered = all_accepted or spec.distance is None
         stochastic = getattr(spec, "stochastic", None) is not None and not all_accepted
         # the accept tail (abc_pnorm_accept): a p-norm distance and the
         # uniform acceptor decided in one pass over the user simulator's
         # rows, no distance array; the kept rows' distances afterwards
         pnorm_tail = None
-        if not (stochastic or all_accepted or spec.distance is None) and \
-                hasattr(spec.distance, "fused_pnorm"):
+        if not (stochastic or unfiltered) and hasattr(spec.distance, "fused_pnorm"):
             pnorm_tail = spec.distance.fused_pnorm(spec.t, spec.sum_stat_keys, dev)
         # StochasticAcceptor + record_rejected: keep every evaluated
         # candidate's (theta, density, key, ancestor) for the temperature
         rec_extra = [] if (stochastic and record) else None
-        keeps = []          # per round: accepted rows kept by each rank
-        rec_keeps = []      # per round: recorded rows of each rank
-        rec_left = self._record_limit(len(spec.sum_stat_keys))
-        cut = None          # ws > 1: the last round's cutoff, resolved in _assemble
-        n_acc = 0
-        base = 0
-        n_eval = 0
-        ok = True
-        rounds = 0
-        while n_acc < n:
-            if self.check_max_eval and n_eval >= max_eval:
-                ok = False
+        led = self._ledger(n, rank, ws, S)
+        while led.need > 0:
+            if self.check_max_eval and led.n_eval >= max_eval:
                 break
-            B = self._limit_to_max_eval(self._round_size(n - n_acc, ws, d,
-                                                         len(spec.sum_stat_keys)), max_eval,
-                                        n_eval, ws)
-            lo, _ = dd.rank_range(base, B, rank)
+            B = self._limit_to_max_eval(self._round_size(led.need, ws, d, S),
+                                        max_eval, led.n_eval, ws)
+            kk = min(led.need, B)
+            lo, _ = dd.rank_range(led.base, B, rank)
             theta, lp, anc, att = self._propose(spec, B, seed, gen, lo, d)
             if spec.transition is None and getattr(spec, "host_prior", None):
                 # t = 0: the host-scipy leg draws its coordinates as ppf of
@@ -260,19 +416,11 @@ class BatchedGPUSampler(Sampler):
             if pnorm_tail is not None:
                 if x.dtype != gpu.F64 or not x.is_contiguous():
                     x = x.to(gpu.F64).contiguous()
-                kk = min(n - n_acc, B)
                 idx, cnt = gpu.pnorm_accept(x, spec.x0vec, *pnorm_tail, spec.eps,
                                             kk, att=att, max_attempts=self.max_attempts)
-                if ws == 1:
-                    both = gpu.torch.cat([cnt.view(1), idx[kk - 1:kk]]).cpu()
-                    cnt_local = int(both[0])
-                    pos_hint = int(both[1])
-                else:
-                    cnt_local = cnt
-            elif all_accepted or spec.distance is None:
+            elif unfiltered:
                 dist = gpu.torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
                 idx = gpu.torch.arange(B, dtype=gpu.I64, device=dev)
-                cnt_local = B
             else:
                 dist = spec.distance.device_call(x, spec.x0vec, spec.t,
                                                  spec.sum_stat_keys)
@@ -299,39 +447,18 @@ class BatchedGPUSampler(Sampler):
                     idx, cnt = gpu.accept_compact(key, 0.0)
                 else:
                     idx, cnt = gpu.accept_compact(dist, spec.eps)
-                if ws == 1:
-                    # one read: the count and the index of the n-th accepted
-                    # (meaningful only when this round completes the sample)
-                    kk = min(n - n_acc, B)
-                    tail = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
-                    both = gpu.torch.cat([cnt.view(1), tail]).cpu()
-                    cnt_local = int(both[0])
-                    pos_hint = int(both[1])
-                else:
-                    cnt_local = cnt        # gathered on the device, one host read
-            counts = dd.allgather_counts(cnt_local, dev)
-            keep = dd.cutoff(counts, n - n_acc)
-            total_keep = int(keep.sum())
-            k_mine = int(keep[rank])
-            # evaluations up to the cutoff (global order); rec_all = recorded
-            # rows of every rank this round (identical on all ranks)
-            rec_all = np.full(ws, B, dtype=np.int64)
-            if n_acc + total_keep >= n:
-                c_rank = int(np.nonzero(keep)[0][-1])
-                if ws > 1:
-                    # the cutoff position travels in the generation's packed
-                    # row gather (_assemble), not in a collective of its own
-                    cut = self._pending_cut(idx, keep, c_rank, rank, B, dev)
-                    evaluated = 0
-                else:
-                    pos = (pos_hint if not (all_accepted or spec.distance is None)
-                           else self._local_cutoff_pos(idx, keep[c_rank]))
-                    evaluated = c_rank * B + pos + 1
-                    rec_all[c_rank] = pos + 1
-                    rec_all[c_rank + 1:] = 0
+            if unfiltered:
+                # idx is arange(B): the k-th kept is candidate k - 1, no read
+                cnt_local, pos = B, kk - 1
+            elif ws == 1:
+                # one read: the count and the index of the n-th accepted
+                # (meaningful only when this round completes the sample)
+                tail = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
+                cnt_local, pos = gpu.torch.cat([cnt.view(1), tail]).cpu().tolist()
             else:
-                evaluated = ws * B
-            rec_rows = int(rec_all[rank])
+                cnt_local, pos = cnt, None    # gathered on the device, one host read
+            counts = dd.allgather_counts(cnt_local, dev)
+            k_mine, rec_rows = led.settle(counts, B, idx, pos, record)
             if k_mine:
                 sel = idx[:k_mine]
                 lp_cols = [lp] if lp is not None else []
@@ -353,68 +480,29 @@ class BatchedGPUSampler(Sampler):
                     # kept rows only: the bits the proposal kernel would have
                     # written (same device function)
                     got[1] = gpu.prior_logpdf(got[0], spec.prior_kind, spec.prior_params)
-                    if (all_accepted or spec.distance is None) and att is not None:
+                    if unfiltered and att is not None:
                         # this branch keeps rows 0..k-1 unfiltered, including
                         # proposals that exhausted max_attempts: their last
                         # draw's density is not the proposal's, and the
                         # proposal kernel would have written -inf (weight 0)
                         gpu.mask_gave_up(got[1], att[:k_mine], self.max_attempts, -np.inf)
-                acc_theta.append(got[0])
-                acc_lp.append(got[1])
-                acc_d.append(got[2])
-                acc_x.append(got[3])
+                for k, v in zip(("theta", "lp", "dist", "x"), got):
+                    kept[k].append(v)
                 if anc is not None:
-                    acc_anc.append(got[4])
+                    kept["anc"].append(got[4])
                 if stochastic:
-                    acc_w.append(got[-1])
-            if record and cut is not None:
-                # rows trimmed once the cutoff position is known (_finish_cut)
-                rec_x.append(x)
-                rec_keeps.append(None)
+                    kept["w"].append(got[-1])
+            if record:
+                # a pending multi-rank cut keeps the whole round's rows,
+                # trimmed once the cutoff position is known (_finish)
+                rr = B if rec_rows is None else rec_rows
+                rec_x.append(x[:rr].clone() if rr < B // 2 else x[:rr])
                 if rec_extra is not None:
-                    rec_extra.append((theta, dist, key, anc))
-            elif record:
-                rec_all, rec_left = self._cap_records(rec_all, rec_left)
-                rec_rows = int(rec_all[rank])
-                rec_x.append(x[:rec_rows].clone() if rec_rows < B // 2 else x[:rec_rows])
-                rec_keeps.append(rec_all)
-                if rec_extra is not None:
-                    rec_extra.append((theta[:rec_rows], dist[:rec_rows],
-                                      key[:rec_rows],
-                                      None if anc is None else anc[:rec_rows]))
-            keeps.append(keep)
-            n_acc += total_keep
-            n_eval += evaluated
-            base += ws * B
-            rounds += 1
-            tot_cnt = int(counts.sum())
-            self._acc_rate = max(tot_cnt / float(ws * B), 1e-6)
-        if n_acc < n:
-            ok = False
-        cols = self._assemble(spec, acc_theta, acc_lp, acc_d, acc_x, dev, d,
-                              all_accepted, keeps, acc_anc, acc_w, cut=cut)
-        if cut is not None:
-            n_eval, rec_left = self._finish_cut(cut, n_eval, rec_left, rec_keeps,
-                                                rec_x if record else None,
-                                                rec_extra, rank, ws)
-        self.nr_evaluations_ = int(n_eval)
-        self.last_stats = dict(rounds=rounds, evaluations=int(n_eval),
-                               accepted=int(n_acc),
-                               records_truncated=self._records_truncated)
-        recorded = None
-        records = None
-        if record:
-            recorded = self._gather_recorded(rec_x, rec_keeps, dev, ws)
-            if rec_extra:
-                parts = list(zip(*rec_extra))
-                records = tuple(
-                    None if any(a is None for a in col)
-                    else self._gather_recorded(list(col), rec_keeps, dev, ws)
-                    for col in parts)
-        elif cols is not None:
-            recorded = cols.sum_stats
-        return ColumnarSample(cols, recorded, spec.sum_stat_keys,
-                              record, ok and n_acc == n, records=records)
+                    rec_extra.append((theta[:rr], dist[:rr], key[:rr],
+                                      None if anc is None else anc[:rr]))
+            self._acc_rate = max(int(counts.sum()) / float(ws * B), 1e-6)
+        return self._finish(spec, led, kept, rec_x if record else None, rec_extra,
+                            dev, d, all_accepted)
 
     def _sample_per_candidate(self, n, simulate_one, max_eval):
         """A closure the batched kernels cannot run -- a plain
@@ -540,32 +628,9 @@ class BatchedGPUSampler(Sampler):
         left = int(math.ceil(max_eval)) - int(n_eval)
         return int(max(1, min(B, left // ws)))
 
-    def _record_limit(self, S):
-        self._records_truncated = False
-        if self.record_device_budget_bytes is None:
-            self._budget_capped = False
-            return self.max_nr_recorded
-        budget_rows = self.record_device_budget_bytes // (8 * max(S, 1))
-        self._budget_capped = budget_rows < self.max_nr_recorded
-        return min(self.max_nr_recorded, budget_rows)
-
-    def _cap_records(self, rec_all, rec_left):
-        """Keep only the first max_nr_recorded recorded candidates in global
-        order (round-major, then rank); returns (rows per rank, rows left)."""
-        if not np.isfinite(rec_left):
-            return rec_all, rec_left
-        out = np.zeros_like(rec_all)
-        left = int(rec_left)
-        for q in range(len(rec_all)):
-            out[q] = min(int(rec_all[q]), left)
-            left -= int(out[q])
-        if left == 0 and out.sum() < rec_all.sum() and self._budget_capped:
-            if not self._records_truncated:
-                logger.warning("recorded sum stats exceed record_device_budget_bytes "
-                               "(%d); keeping the first rows only",
-                               self.record_device_budget_bytes)
-            self._records_truncated = True
-        return out, left
+    def _ledger(self, n, rank, ws, S):
+        return _RoundLedger(n, rank, ws, S, self.max_nr_recorded,
+                            self.record_device_budget_bytes)
 
     def _sample_fused(self, n, fr, spec, max_eval, record, dev, rank, ws):
         """sample_until_n_accepted on fused rounds: per round one
@@ -574,30 +639,26 @@ class BatchedGPUSampler(Sampler):
         (abc_candidates_regen) bit-identical to the staged kernels."""
         torch = gpu.torch
         S = len(spec.sum_stat_keys)
-        cols = {k: [] for k in ("theta", "lp", "dist", "x", "anc")}
-        rec_x, rec_keeps, keeps = [], [], []
+        rec_x = []
         arena, arena_off = None, 0
         # kept rows: pooled buffers filled through raw addresses (one set of
         # views per buffer, built after the loop)
         kept, kept_off, kept_segs = None, 0, []
         row_bytes = (8 * fr.d, 8, 8, 8 * S, 8)
-        rec_left = self._record_limit(S)
-        cut = None
-        n_acc = n_eval = base = rounds = 0
-        ok = True
+        led = self._ledger(n, rank, ws, S)
         rate, measured = self._acc_rate, False
         tot_B = tot_cnt = 0
         filtered = reruns = 0
-        while n_acc < n:
-            if self.check_max_eval and n_eval >= max_eval:
-                ok = False
+        while led.need > 0:
+            if self.check_max_eval and led.n_eval >= max_eval:
                 break
-            need = n - n_acc
+            need = led.need
             B = self._limit_to_max_eval(self._fused_size(need, ws, rate, measured, S, record),
-                                        max_eval, n_eval, ws)
-            lo, _ = dd.rank_range(base, B, rank)
+                                        max_eval, led.n_eval, ws)
+            kk = min(need, B)
+            lo, _ = dd.rank_range(led.base, B, rank)
             rx = None
-            if record and rec_left > 0:
+            if record and led.rec_left > 0:
                 # recorded rows of consecutive rounds land back to back in one
                 # arena (the next round starts after the rows this one keeps),
                 # so the generation's matrix is a view, not a concatenation
@@ -611,42 +672,41 @@ class BatchedGPUSampler(Sampler):
             # the generation's first round takes the threshold on the device
             # (queued behind the quantile kernel, no host wait); later rounds
             # the host value, which has arrived by then
-            thr = getattr(spec, "eps_device", None) if rounds == 0 else None
+            thr = getattr(spec, "eps_device", None) if led.rounds == 0 else None
             if thr is not None:
                 idx, cnt = fr.run(lo, B, 0.0, cap=need, filter=filt, rec_x=rx,
                                   eps_dev=thr[0], eps_scale=thr[1])
             else:
                 idx, cnt = fr.run(lo, B, spec.eps, cap=need, filter=filt, rec_x=rx)
-            pair = self._queue_pair(cnt, idx, min(need, B) - 1) if ws == 1 else None
             if ws == 1:
+                # one read: the count and the index of the need-th accepted
                 n_keep = cnt
+                self._reader.queue(cnt, idx[kk - 1:kk])
             else:
                 # several ranks: the round's counts are all-gathered on the
                 # device and this rank's share of the first `need` accepted
                 # (global order) is computed there, so the regeneration is
-                # queued before any host read, as on one rank
+                # queued before any host read, as on one rank; the host reads
+                # the gathered counts for its bookkeeping
                 gathered = dd.allgather_counts_device(cnt)
                 n_keep = gpu.round_keep(gathered, need, rank)
-                pair = self._queue_counts(gathered)
+                self._reader.queue(gathered)
             # the kept rows' regeneration is queued before the count read,
             # sized on the device (the kept rows into the pooled buffer), so
             # the GPU is busy while the host reads the count
-            if kept is None or kept_off + min(need, B) > kept[1]:
+            if kept is None or kept_off + kk > kept[1]:
                 if kept is not None and kept_off:
                     kept_segs.append((kept[0], kept_off))
-                views = self._kept_buffers(min(need, B), fr.d, S, dev)
+                views = self._kept_buffers(kk, fr.d, S, dev)
                 kept = (views, views[0].shape[0], [v.data_ptr() for v in views])
                 kept_off = 0
-            fr.regen_into(lo, idx.data_ptr(), min(need, B),
+            fr.regen_into(lo, idx.data_ptr(), kk,
                           [a + kept_off * b for a, b in zip(kept[2], row_bytes)],
                           n_dev=n_keep)
+            counts = self._reader.wait()
+            pos = None
             if ws == 1:
-                # one read: the count and the index of the need-th accepted
-                cnt_local, pos_hint = self._wait_pair(pair)
-                counts = dd.allgather_counts(cnt_local, dev)
-            else:
-                # the gathered counts, for the host's bookkeeping
-                counts = self._wait_counts(pair)
+                counts, pos = counts[:1], int(counts[1])
             if thr is not None:
                 spec.eps_device = None
                 if np.isnan(thr[2].get()[0]):
@@ -656,47 +716,19 @@ class BatchedGPUSampler(Sampler):
                     # value (the sort-based rerun, gpu.resolve_quantile).
                     # Every rank holds the same quantile, so all re-run
                     reruns += 1
-                    spec.eps
                     continue
-            keep = dd.cutoff(counts, need)
-            total_keep = int(keep.sum())
-            k_mine = int(keep[rank])
-            rec_all = np.full(ws, B, dtype=np.int64)
-            if n_acc + total_keep >= n:
-                c_rank = int(np.nonzero(keep)[0][-1])
-                if ws > 1:
-                    cut = self._pending_cut(idx, keep, c_rank, rank, B, dev)
-                    evaluated = 0
-                else:
-                    pos = pos_hint
-                    evaluated = c_rank * B + pos + 1
-                    rec_all[c_rank] = pos + 1
-                    rec_all[c_rank + 1:] = 0
-            else:
-                evaluated = ws * B
+            k_mine, rr = led.settle(counts, B, idx, pos, rx is not None)
             kept_off += k_mine              # regenerated before the count read
-            if record and cut is not None and rx is not None:
-                rec_x.append(rx)            # trimmed in _finish_cut
-                rec_keeps.append(None)
-            elif record:
-                if rx is None:
-                    rec_all = np.zeros(ws, dtype=np.int64)
-                rec_all, rec_left = self._cap_records(rec_all, rec_left)
-                rr = int(rec_all[rank])
-                if rx is not None:
-                    rec_x.append(rx[:rr])
-                    arena_off += rr
-                rec_keeps.append(rec_all)
-            keeps.append(keep)
-            n_acc += total_keep
-            n_eval += evaluated
-            base += ws * B
-            rounds += 1
+            if rx is not None:
+                # a pending multi-rank cut keeps the round whole (_finish trims)
+                rec_x.append(rx if rr is None else rx[:rr])
+                arena_off += rr or 0
             tot_B += ws * B
             tot_cnt += int(counts.sum())
             rate, measured = max(int(counts.sum()) / float(ws * B), 1e-12), True
         if kept is not None and kept_off:
             kept_segs.append((kept[0], kept_off))
+        cols = {k: [] for k in self._KEPT}
         for views, cnt in kept_segs:
             th, lp, anc, x, dist = (v[:cnt] for v in views)
             for k, v in zip(("theta", "lp", "dist", "x", "anc"), (th, lp, dist, x, anc)):
@@ -705,78 +737,47 @@ class BatchedGPUSampler(Sampler):
         if self._acc_rate:
             self._acc_trend = min(1.0, max(0.5, new_rate / self._acc_rate))
         self._acc_rate = new_rate
-        if n_acc < n:
-            ok = False
-        out = self._assemble(spec, cols["theta"], cols["lp"], cols["dist"],
-                             cols["x"], dev, fr.d, False, keeps,
-                             cols["anc"] if spec.transition is not None else (),
-                             cut=cut)
-        if cut is not None:
-            n_eval, rec_left = self._finish_cut(cut, n_eval, rec_left, rec_keeps,
-                                                rec_x if record else None, None,
-                                                rank, ws)
-        self.nr_evaluations_ = int(n_eval)
-        self.last_stats = dict(rounds=rounds, evaluations=int(n_eval),
-                               accepted=int(n_acc), fused=True,
-                               candidates=int(tot_B), filtered_rounds=filtered,
-                               quantile_reruns=reruns,
-                               records_truncated=self._records_truncated)
-        recorded = None
-        if record:
-            recorded = self._gather_recorded(rec_x, rec_keeps, dev, ws)
-            if recorded is None:
-                recorded = torch.empty((0, S), dtype=gpu.F64, device=dev)
-        elif out is not None:
-            recorded = out.sum_stats
-        return ColumnarSample(out, recorded, spec.sum_stat_keys, record,
-                              ok and n_acc == n)
+        sample = self._finish(spec, led, cols, rec_x if record else None, None,
+                              dev, fr.d, False, fused=True, candidates=int(tot_B),
+                              filtered_rounds=filtered, quantile_reruns=reruns)
+        if record and sample._recorded is None:
+            # no round recorded a row: an empty matrix here
+            sample._recorded = torch.empty((0, S), dtype=gpu.F64, device=dev)
+        return sample
 
-    def _queue_pair(self, cnt, idx, k):
-        """Queue the round's (count, idx[k]) into a cached pinned pair (two
-        async copies, no concatenation kernel, no allocation) and an event;
-        _wait_pair reads it.  Work queued after the event (the kept rows'
-        regeneration) runs while the host waits."""
-        torch = gpu.torch
-        if cnt.device.type != "cuda":              # host tensors (test doubles)
-            return (int(cnt.reshape(-1)[0]), int(idx[k]))
-        hp = getattr(self, "_pair_host", None)
-        if hp is None:
-            hp = self._pair_host = torch.empty(2, dtype=torch.int64, pin_memory=True)
-            self._pair_ev = torch.cuda.Event()
-        hp[0:1].copy_(cnt.reshape(1), non_blocking=True)
-        hp[1:2].copy_(idx[k:k + 1], non_blocking=True)
-        # the stream named by the tensor's device: record() with no stream
-        # resolves the current device through torch.cuda.is_available (~40 us)
-        self._pair_ev.record(torch.cuda.current_stream(cnt.device))
-        return None
+    _KEPT = ("theta", "lp", "dist", "x", "anc", "w")   # columns of kept rows
 
-    def _wait_pair(self, queued):
-        if queued is not None:
-            return queued
-        self._pair_ev.synchronize()
-        return int(self._pair_host[0]), int(self._pair_host[1])
-
-    def _queue_counts(self, gathered):
-        """Queue the all-gathered round counts [ws] into a cached pinned
-        buffer and an event (the multi-rank _queue_pair); _wait_counts
-        reads them."""
-        torch = gpu.torch
-        if not gathered.is_cuda:
-            return gathered.numpy().copy()
-        ws = gathered.numel()
-        hc = getattr(self, "_counts_host", None)
-        if hc is None or hc.numel() != ws:
-            hc = self._counts_host = torch.empty(ws, dtype=torch.int64, pin_memory=True)
-            self._counts_ev = torch.cuda.Event()
-        hc.copy_(gathered, non_blocking=True)
-        self._counts_ev.record(torch.cuda.current_stream(gathered.device))
-        return None
-
-    def _wait_counts(self, queued):
-        if queued is not None:
-            return queued
-        self._counts_ev.synchronize()
-        return self._counts_host.numpy().copy()
+    def _finish(self, spec, led, kept, rec_x, rec_extra, dev, d, all_accepted,
+                **stats):
+        """The end of a generation, the same for every loop: the population
+        from the kept rows (kept: lists of per-round pieces under _KEPT), the
+        pending cut resolved and the last recorded pieces trimmed to it,
+        nr_evaluations_ and last_stats (stats: the loop's own keys), the
+        recorded rows (rec_x, rec_extra: this rank's pieces; None: the
+        generation records nothing) and the sample."""
+        cols, gathered = self._assemble(spec, kept, dev, d, all_accepted, led)
+        rr = led.finish(gathered)
+        if rr is not None:
+            rec_x[-1] = rec_x[-1][:rr]
+            if rec_extra:
+                rec_extra[-1] = tuple(None if a is None else a[:rr]
+                                      for a in rec_extra[-1])
+        self.nr_evaluations_ = int(led.n_eval)
+        self.last_stats = dict(rounds=led.rounds, evaluations=int(led.n_eval),
+                               accepted=int(led.n_acc), **stats,
+                               records_truncated=led.records_truncated)
+        recorded = records = None
+        if rec_x is not None:
+            recorded = self._gather_recorded(rec_x, led.rec_keeps, dev, led.ws)
+            if rec_extra:
+                records = tuple(
+                    None if any(a is None for a in col)
+                    else self._gather_recorded(list(col), led.rec_keeps, dev, led.ws)
+                    for col in zip(*rec_extra))
+        elif cols is not None:
+            recorded = cols.sum_stats
+        return ColumnarSample(cols, recorded, spec.sum_stat_keys,
+                              rec_x is not None, led.n_acc == led.n, records=records)
 
     # population columns of the fused rounds are carved from pooled device
     # arenas: a generation's new population (kept by the History) would
@@ -791,7 +792,7 @@ class BatchedGPUSampler(Sampler):
         pieces = (((cap, d), cap * d), ((cap,), cap), ((cap,), cap),
                   ((cap, S), cap * S), ((cap,), cap))
         need = sum(n_el + (-n_el) % 32 for _, n_el in pieces)   # 256-byte aligned
-        pool, off = getattr(self, "_pool", (None, 0))
+        pool, off = self._pool
         if pool is None or pool.device != dev or off + need > pool.numel():
             pool = torch.empty(max(need, self._POOL_BYTES // 8), dtype=gpu.F64, device=dev)
             off = 0
@@ -829,47 +830,6 @@ class BatchedGPUSampler(Sampler):
             return a.as_strided((n, a.shape[1]), a.stride())
         return torch.cat(pieces, 0)
 
-    @staticmethod
-    def _local_cutoff_pos(idx, k):
-        return int(idx[int(k) - 1].item())
-
-    @staticmethod
-    def _pending_cut(idx, keep, c_rank, rank, B, dev):
-        """The completing round of a multi-rank generation: the cut rank's
-        local position of its last kept candidate stays on the device (no
-        host read, no collective of its own) and rides in the packed row
-        gather of _assemble; every other rank sends -1."""
-        torch = gpu.torch
-        if rank == c_rank:
-            k = int(keep[c_rank])
-            pos = idx[k - 1:k].to(gpu.F64)
-        else:
-            pos = torch.full((1,), -1.0, dtype=gpu.F64, device=dev)
-        return dict(c_rank=c_rank, B=int(B), pos=pos)
-
-    def _finish_cut(self, cut, n_eval, rec_left, rec_keeps, rec_x, rec_extra,
-                    rank, ws):
-        """Resolve the pending cutoff once _assemble has gathered the cut
-        rank's position: evaluations up to the n-th accepted (global order),
-        the last round's recorded rows per rank (capped like every round), and
-        this rank's recorded pieces of that round trimmed to them."""
-        c_rank, B = cut["c_rank"], cut["B"]
-        pos = int(cut["gathered"][c_rank])
-        n_eval += c_rank * B + pos + 1
-        if rec_x is not None and rec_keeps and rec_keeps[-1] is None:
-            rec_all = np.full(ws, B, dtype=np.int64)
-            rec_all[c_rank] = pos + 1
-            rec_all[c_rank + 1:] = 0
-            rec_all, rec_left = self._cap_records(rec_all, rec_left)
-            rr = int(rec_all[rank])
-            rec_keeps[-1] = rec_all
-            if rec_x and rec_x[-1].shape[0] != rr:
-                rec_x[-1] = rec_x[-1][:rr]
-            if rec_extra:
-                rec_extra[-1] = tuple(None if a is None else a[:rr]
-                                      for a in rec_extra[-1])
-        return n_eval, rec_left
-
     def _proposal_round(self, spec, seed, gen, dev):
         """A proposal-only gpu.CandidateRound of this generation (dummy
         simulator / distance fields, never read), cached per generation:
@@ -881,8 +841,8 @@ class BatchedGPUSampler(Sampler):
         if len(spec.param_names) > self.FUSED_MAX_DIM:
             return None     # d > 64: the transition's own (wide) proposal kernel
         key = (seed, gen)
-        if getattr(self, "_prop_spec", None) is spec and self._prop_key == key:
-            return self._prop_round
+        if self._prop[0] is spec and self._prop[1] == key:
+            return self._prop[2]
         arrays = None
         if spec.transition is not None:
             fn = getattr(spec.transition, "proposal_arrays", None)
@@ -895,7 +855,7 @@ class BatchedGPUSampler(Sampler):
                                 spec.prior_params, torch.zeros(1, dtype=torch.int32, device=dev),
                                 z, z, z, z, 2.0, seed, gen, self.max_attempts,
                                 **(arrays or {}))
-        self._prop_spec, self._prop_key, self._prop_round = spec, key, fr
+        self._prop = (spec, key, fr)
         return fr
 
     def _propose(self, spec, B, seed, gen, lo, d):
@@ -918,48 +878,10 @@ class BatchedGPUSampler(Sampler):
                 generation=gen, idx0=lo, max_attempts=self.max_attempts)
         return th, lp, anc, att
 
-    @staticmethod
-    def global_order(keeps):
-        """Permutation from the rank-major all-gather (rank 0's rows of every
-        round, then rank 1's, ...) to global candidate-index order (round
-        major, then rank), from the per-round keep counts [rounds x ranks]."""
-        k = np.asarray(keeps, dtype=np.int64).reshape(len(keeps), -1)
-        if k.size == 0:
-            return np.zeros(0, dtype=np.int64)
-        rank_start = np.concatenate([[0], np.cumsum(k.sum(0))[:-1]])
-        round_off = np.cumsum(k, axis=0) - k          # [rounds x ranks]
-        starts = (rank_start[None, :] + round_off).ravel()   # round-major
-        lens = k.ravel()
-        tot = int(lens.sum())
-        base = np.repeat(starts - np.concatenate([[0], np.cumsum(lens)[:-1]]),
-                         lens)
-        return base + np.arange(tot, dtype=np.int64)
-
-    @staticmethod
-    def global_pieces(keeps):
-        """The permutation of global_order as contiguous pieces (start, len)
-        of the rank-major array, in global order (rounds x ranks pieces)."""
-        k = np.asarray(keeps, dtype=np.int64).reshape(len(keeps), -1)
-        if k.size == 0:
-            return []
-        rank_start = np.concatenate([[0], np.cumsum(k.sum(0))[:-1]])
-        round_off = np.cumsum(k, axis=0) - k
-        starts = (rank_start[None, :] + round_off).ravel()
-        return [(int(a), int(n)) for a, n in zip(starts, k.ravel()) if n > 0]
-
-    @staticmethod
-    def reorder(t, pieces):
-        """Rows of t in the order of the pieces (one concatenation)."""
-        if len(pieces) <= 1:
-            return t
-        if all(a == b[0] + b[1] for b, (a, _) in zip(pieces[:-1], pieces[1:])) \
-                and pieces[0][0] == 0:
-            return t          # already in order
-        return gpu.torch.cat([t[a:a + n] for a, n in pieces], 0)
-
-    def _assemble(self, spec, acc_theta, acc_lp, acc_d, acc_x, dev, d,
-                  all_accepted, keeps, acc_anc=(), acc_w=(), cut=None):
-        rank, ws = dd.world()
+    def _assemble(self, spec, kept, dev, d, all_accepted, led):
+        """(population of the kept rows, weighted and gathered over the ranks
+        in global order; the ranks' cutoff positions of a pending cut, else
+        None).  kept: per-round pieces of the columns _KEPT."""
         torch = gpu.torch
         def cat(lst):
             if len(lst) == 1:
@@ -967,8 +889,9 @@ class BatchedGPUSampler(Sampler):
             if lst[0].dim() == 2:
                 return self._join_rows(lst)
             return self._join_rows([t.view(-1, 1) for t in lst]).view(-1)
-        if acc_theta:
-            theta, lp, dist, x = cat(acc_theta), cat(acc_lp), cat(acc_d), cat(acc_x)
+        rounds = len(kept["theta"])
+        if rounds:
+            theta, lp, dist, x = (cat(kept[k]) for k in ("theta", "lp", "dist", "x"))
         else:
             S = len(spec.sum_stat_keys)
             theta = torch.empty((0, d), dtype=gpu.F64, device=dev)
@@ -977,7 +900,7 @@ class BatchedGPUSampler(Sampler):
             x = torch.empty((0, S), dtype=gpu.F64, device=dev)
         # importance weights for this rank's accepted rows (smc.py:768-811);
         # a StochasticAcceptor's acceptance weights multiply in
-        accw = cat(acc_w) if acc_w and len(acc_w) == len(acc_theta) else None
+        accw = cat(kept["w"]) if rounds and len(kept["w"]) == rounds else None
         if all_accepted:
             w = torch.ones(theta.shape[0], dtype=gpu.F64, device=dev)
         elif spec.transition is None:
@@ -987,8 +910,7 @@ class BatchedGPUSampler(Sampler):
         else:
             # ancestors of the accepted rows: population rows near them,
             # used by the x3 density kernel as exponent offsets
-            anc = (cat(acc_anc) if acc_anc and
-                   len(acc_anc) == len(acc_theta) else None)
+            anc = cat(kept["anc"]) if rounds and len(kept["anc"]) == rounds else None
             lt = spec.transition.logpdf_device(theta, hint=anc)
             hook, self.on_density_queued = self.on_density_queued, None
             if hook is not None:
@@ -998,17 +920,18 @@ class BatchedGPUSampler(Sampler):
                 lp = lp + hl      # the host-scipy leg's density factors
             w = gpu.importance_weights(lp, lt, spec.weight_scale,
                                        acc_w=None if accw is None else accw.contiguous())
-        if ws > 1:
+        gathered = None       # the ranks' cutoff positions (_RoundLedger.finish)
+        if led.ws > 1:
             # one packed all-gather; the rows come back in global
             # candidate-index order so the population (and every later draw
             # keyed on it) is the same for any number of ranks
             # (the cut rank's cutoff position rides in the same collective)
             parts = [theta, w, dist, x]
-            extra = None if cut is None else cut["pos"]
+            extra = None if led.cut is None else led.cut["pos"]
             if len({a.dtype for a in parts}) == 1:
-                got = dd.allgather_rows_ordered(parts, keeps, dev, extra=extra)
+                got = dd.allgather_rows_ordered(parts, led.keeps, dev, extra=extra)
             else:
-                got = [dd.allgather_rows_ordered([a], keeps, dev,
+                got = [dd.allgather_rows_ordered([a], led.keeps, dev,
                                                  extra=extra if i == 0 else None)
                        for i, a in enumerate(parts)]
                 if extra is not None:
@@ -1016,10 +939,10 @@ class BatchedGPUSampler(Sampler):
                 else:
                     got = [g[0] for g in got]
             if extra is not None:
-                got, cut["gathered"] = got
+                got, gathered = got
             theta, w, dist, x = got
         if theta.shape[0] == 0:
-            return None
+            return None, gathered
         return ColumnarParticles(theta.contiguous(), w.contiguous(),
                                  dist.contiguous(), x.contiguous(),
-                                 spec.param_names, spec.sum_stat_keys, m=0)
+                                 spec.param_names, spec.sum_stat_keys, m=0), gathered

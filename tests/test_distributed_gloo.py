@@ -215,12 +215,17 @@ class _FusedRound:
             ctypes.memmove(ptr, r.ctypes.data, r.nbytes)
 
 
-def _run(n, eps, batch, record, fused=False, nan_first=False):
+def _run(n, eps, batch, record, fused=False, nan_first=False, max_rec=None,
+         budget=None):
     """fused: False (staged distance + compaction), True (fused rounds) or
     "tail" (staged rounds with the accept tail); nan_first: the first fused
-    round gets an undecided (NaN) device threshold."""
+    round gets an undecided (NaN) device threshold; max_rec: the sampler's
+    max_nr_recorded; budget: its record_device_budget_bytes."""
     from pyabc_amd.sampler import BatchedGPUSampler
-    s = BatchedGPUSampler(batch_size=batch, seed=SEED, fused=fused is True)
+    s = BatchedGPUSampler(batch_size=batch, seed=SEED, fused=fused is True,
+                          record_device_budget_bytes=budget)
+    if max_rec is not None:
+        s.max_nr_recorded = max_rec
     if fused is True:
         s._fused_round = lambda spec, seed, gen, dev: _FusedRound(spec)
     s.sample_factory.record_rejected = record
@@ -233,6 +238,7 @@ def _run(n, eps, batch, record, fused=False, nan_first=False):
                 n_eval=np.array(s.nr_evaluations_),
                 rounds=np.array(s.last_stats["rounds"]),
                 reruns=np.array(s.last_stats.get("quantile_reruns", 0)),
+                trunc=np.array(s.last_stats["records_truncated"]),
                 rec=(rec.numpy() if rec is not None else np.zeros(0)))
 
 
@@ -324,6 +330,67 @@ def test_sharded_fused_quantile_rerun(monkeypatch, n, batch, record):
                 np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
             if record:
                 np.testing.assert_array_equal(got["rec"], ref["rec"])
+
+
+# record caps of test_record_cap: (max_nr_recorded, record_device_budget_bytes).
+# The uncapped reference records 1216 rows in 5 rounds of 256: inside the
+# first round, exactly one round, across a round boundary, one short of the
+# cutoff, at the cutoff, beyond it; then a device budget of 200 rows of 3 f64
+_RECORD_CAPS = [(1, None), (100, None), (256, None), (293, None), (1215, None),
+                (1216, None), (1266, None), (None, 8 * 3 * 200)]
+
+
+def _cap_worker(rank, ws, port, out_dir, n, eps, batch, fused):
+    """Every record cap on one set of gloo ranks (one spawn for all cases)."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=ws)
+    try:
+        _install_cpu_doubles(setattr)
+        res = {}
+        for i, (m, budget) in enumerate(_RECORD_CAPS):
+            got = _run(n, eps, batch, True, fused, max_rec=m, budget=budget)
+            res.update({f"{k}{i}": v for k, v in got.items()})
+        np.savez(os.path.join(out_dir, f"r{rank}.npz"), **res)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("fused", [False, True, "tail"])
+def test_record_cap(monkeypatch, fused):
+    """max_nr_recorded = m keeps exactly the first m recorded candidates of
+    the uncapped run (global index order) and changes nothing else: the same
+    population and evaluations, records_truncated False.  A
+    record_device_budget_bytes of 200 rows keeps the first 200 and sets
+    records_truncated.  Staged, fused and accept-tail loops, on 1 rank
+    (round size 256) and on 2 gloo ranks (128 each), against the uncapped
+    one-rank staged run."""
+    n, eps, batch, ws = 300, 1.6, 128, 2
+    _install_cpu_doubles(monkeypatch.setattr)
+    ref = _run(n, eps, batch * ws, True, False)
+    assert ref["rec"].shape == (1216, D) and int(ref["rounds"]) == 5
+    assert not bool(ref["trunc"])
+
+    def check(got, m, budget):
+        rows = 200 if budget is not None else m
+        np.testing.assert_array_equal(got["rec"], ref["rec"][:rows])
+        assert int(got["n_eval"]) == int(ref["n_eval"])
+        assert bool(got["trunc"]) == (budget is not None)
+        for k in ("theta", "w", "d", "x"):
+            np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
+
+    for m, budget in _RECORD_CAPS:
+        check(_run(n, eps, batch * ws, True, fused, max_rec=m, budget=budget),
+              m, budget)
+    with tempfile.TemporaryDirectory() as tmp:
+        mp.start_processes(_cap_worker, args=(ws, _free_port(), tmp, n, eps,
+                                              batch, fused),
+                           nprocs=ws, join=True, start_method="spawn")
+        for rank in range(ws):
+            r = np.load(os.path.join(tmp, f"r{rank}.npz"))
+            for i, (m, budget) in enumerate(_RECORD_CAPS):
+                check({k: r[f"{k}{i}"] for k in ("rec", "n_eval", "trunc",
+                                                 "theta", "w", "d", "x")},
+                      m, budget)
 
 
 def _collective_worker(rank, ws, port, out_dir):
