@@ -499,7 +499,8 @@ int abc_bootstrap_cv(const double* logdens, int64_t B, int64_t N,
  *   1 IndependentLaplaceKernel (par = scale[K], c = sum log(2 scale)),
  *   2 NormalKernel (U [K x r] with U U^T = pinv(cov), c = r log 2pi + log pdet),
  *   3 PoissonKernel, 4 BinomialKernel (par[0] = p), 5 NegativeBinomialKernel
- *   (par[0] = p).  ret_lin: write exp(log pdf) (SCALE_LIN).
+ *   (par[0] = p; NaN at p = 0, as scipy's nbinom).  ret_lin: write
+ *   exp(log pdf) (SCALE_LIN).
  *   Replaces StochasticKernel.__call__ (kernel.py:207-226, 285-303, 361-378,
  *   426-445, 478-495, 533-552).
  * abc_stochastic_accept: StochasticAcceptor.__call__ (acceptor.py:434-476)
@@ -513,7 +514,9 @@ int abc_bootstrap_cv(const double* logdens, int64_t B, int64_t N,
  *   lr - lr_sub (log t_pd - log t_pd_prev; lr_sub may be NULL) shifted by
  *   `shift`; for mode 1, lr holds the linear population weights; mode 2
  *   writes max(lr - lr_sub); mode 3 = mode 0 with linear record weights in
- *   lr.  out[2] device doubles. */
+ *   lr.  In modes 0 and 3 a record whose density is NaN (always rejected by
+ *   abc_stochastic_accept) adds its weight to the denominator out[1] and
+ *   nothing to the numerator out[0].  out[2] device doubles. */
 int abc_kernel_logpdf(const double* x, int64_t B, int S, const int32_t* cols,
                       int K, const double* x0k, int kind, const double* par,
                       const double* U, int r, double c, int ret_lin,

@@ -83,7 +83,8 @@ __global__ __launch_bounds__(256) void kernel_logpdf_kernel(
         s += lgamma(m + 1.0) - (lgamma(k + 1.0) + lgamma(m - k + 1.0)) +
              xlogy(k, p) + xlog1py(m - k, -p);
       } else {                                       // NegBinomial(k; n = m, p)
-        if (!(m > 0.0)) { bad = true; continue; }
+        // scipy's nbinom takes n > 0 and p in (0, 1]: p = 0 is NaN, not -inf
+        if (!(m > 0.0) || !(p > 0.0)) { bad = true; continue; }
         if (k < 0.0) { zero = true; continue; }
         s += lgamma(m + k) - lgamma(k + 1.0) - lgamma(m) + m * log(p) +
              xlog1py(k, -p);
@@ -134,7 +135,8 @@ __device__ __forceinline__ double accept_base(double dv, double pdf_norm,
 // mode 3 (AcceptanceRateScheme, linear weights w = lr):
 //                                 a = sum w_i min(e^{beta l_i}, 1), b = sum w_i
 // with z_i = lr_i - lr_sub_i - shift (log importance weight t_pd / t_pd_prev
-// of record i; lr_sub may be null).
+// of record i; lr_sub may be null).  In modes 0 and 3 a record with a NaN
+// density keeps its weight in b and adds nothing to a.
 __global__ __launch_bounds__(TS_T) void temper_partial_kernel(
     const double* __restrict__ dens, const double* __restrict__ lr,
     const double* __restrict__ lr_sub, int64_t R, double pdf_norm,
@@ -150,12 +152,15 @@ __global__ __launch_bounds__(TS_T) void temper_partial_kernel(
     const double l = accept_base(dens[i], pdf_norm, scale_log);
     // beta == 0: values**0 == 1 even where the base is 0 (temperature.py:741)
     const double bl = (beta == 0.0) ? 0.0 : beta * l;
+    // a NaN density is never accepted (its key is NaN): probability 0, where
+    // fmin(NaN, 0) alone would make it 1
+    const double pacc = isnan(l) ? 0.0 : exp(fmin(bl, 0.0));
     if (mode == 3) {
-      a += lr[i] * exp(fmin(bl, 0.0));
+      a += lr[i] * pacc;
       bsum += lr[i];
     } else if (mode == 0) {
       const double ez = exp(z);
-      a += ez * exp(fmin(bl, 0.0));
+      a += ez * pacc;
       bsum += ez;
     } else {
       const double t = lr[i] * exp(bl);
