@@ -446,6 +446,20 @@ int abc_column_std(const double* X, int64_t R, int S, double* out, void* ws,
 int abc_column_mad(const double* X, int64_t R, int S, double* out, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* AdaptivePNormDistance scale functions, pyabc/distance/scale.py:38-135, per
+ * column of X [R x S] with the observation x0 [S] (device; may be null for
+ * MAD, MEAN_AD and STD, which do not read it).  MAD and STD are the two
+ * entries above, bit for bit; the median kinds are exact order statistics of
+ * fabs(x - centre); the mean kinds make at most two reads of X, the second
+ * centred on the first's mean, and are bitwise reproducible (fixed summation
+ * order, no floating-point atomics). */
+enum { ABC_SCALE_MAD, ABC_SCALE_MEAN_AD, ABC_SCALE_STD, ABC_SCALE_BIAS, ABC_SCALE_RMSD,
+       ABC_SCALE_MAD_TO_OBS, ABC_SCALE_MEAN_AD_TO_OBS, ABC_SCALE_CMAD,
+       ABC_SCALE_CMEAN_AD, ABC_SCALE_STD_TO_OBS };
+size_t abc_column_scale_workspace(int kind, int64_t R, int S);
+int abc_column_scale(int kind, const double* X, int64_t R, int S, const double* x0,
+                     double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- LocalTransition (pyabc/transition/local_transition.py:77-145) -------
  * fit: per particle n, the k nearest other particles (ties by index),
  * weighted covariance of their offsets (weights renormalised, unbiased

@@ -75,6 +75,8 @@ SIGNATURES = {
     "abc_column_stats_workspace": (SZ, [I64, I32]),
     "abc_column_std": (I32, [P, I64, I32, P, P, SZ, P]),
     "abc_column_mad": (I32, [P, I64, I32, P, P, SZ, P]),
+    "abc_column_scale_workspace": (SZ, [I32, I64, I32]),
+    "abc_column_scale": (I32, [I32, P, I64, I32, P, P, P, SZ, P]),
     "abc_local_fit_workspace": (SZ, [I64, I32]),
     "abc_local_fit": (I32, [P, P, I64, I32, I64, D, D, P, P, P, P, P, P, SZ,
                             P]),
@@ -127,6 +129,16 @@ ABC_PROF_DENSITY, ABC_PROF_CANDIDATES, ABC_PROF_REGEN, ABC_PROF_RESCUE = 0, 1, 2
 ABC_PREC_F64 = 0
 ABC_PREC_F32 = 1
 ABC_PREC_X3 = 2
+(ABC_SCALE_MAD, ABC_SCALE_MEAN_AD, ABC_SCALE_STD, ABC_SCALE_BIAS, ABC_SCALE_RMSD,
+ ABC_SCALE_MAD_TO_OBS, ABC_SCALE_MEAN_AD_TO_OBS, ABC_SCALE_CMAD, ABC_SCALE_CMEAN_AD,
+ ABC_SCALE_STD_TO_OBS) = range(10)
+# distance/scale.py's device_kernel tags -> abc_column_scale kinds
+SCALE_KINDS = {"mad": ABC_SCALE_MAD, "mean_ad": ABC_SCALE_MEAN_AD,
+               "std": ABC_SCALE_STD, "bias": ABC_SCALE_BIAS,
+               "rmsd": ABC_SCALE_RMSD, "mad_to_obs": ABC_SCALE_MAD_TO_OBS,
+               "mean_ad_to_obs": ABC_SCALE_MEAN_AD_TO_OBS,
+               "cmad": ABC_SCALE_CMAD, "cmean_ad": ABC_SCALE_CMEAN_AD,
+               "std_to_obs": ABC_SCALE_STD_TO_OBS}
 
 PRIOR_KINDS = {"norm": 0, "uniform": 1, "expon": 2, "laplace": 3,
                "lognorm": 4, "gamma": 5, "beta": 6, "host": 7}

@@ -7,6 +7,10 @@
 // per column of the recorded [R x S] matrix.  np.median: the middle order
 // statistic for odd R, the mean (a + b) / 2 of the two middle ones for even R.
 //
+// The deviation pass takes any per-column centre: with the observation x_0 it
+// is median_absolute_deviation_to_observation (scale.py:88-94), and the MAD
+// plus that is combined_median_absolute_deviation (scale.py:106-114).
+//
 // Layout: the recorded matrix stays row-major [R x S] fp64 (no transposed
 // copy).  Per pass (the median, then the median of |x - median|):
 //   col_sample_kernel   one workgroup per column sorts SMP evenly spaced
@@ -368,15 +372,26 @@ size_t select_ws_bytes(int64_t R, int S) {
   return off + 256;
 }
 
-// out[c] = median_c(|X[:, c] - median_c(X[:, c])|)
-int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
-                      size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  uint64_t* scratch = cv.take<uint64_t>((size_t)R * S);
-  uint64_t* win = cv.take<uint64_t>((size_t)2 * S);
-  unsigned long long* cnt = cv.take<unsigned long long>((size_t)2 * S);
-  double* med = cv.take<double>((size_t)S);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "column_mad: workspace carve");
+// the buffers of one select pass, carved from the caller's workspace
+struct SelectBufs {
+  uint64_t* scratch;
+  uint64_t* win;
+  unsigned long long* cnt;
+  double* med;
+};
+static bool carve_select(Carver& cv, int64_t R, int S, SelectBufs& b) {
+  b.scratch = cv.take<uint64_t>((size_t)R * S);
+  b.win = cv.take<uint64_t>((size_t)2 * S);
+  b.cnt = cv.take<unsigned long long>((size_t)2 * S);
+  b.med = cv.take<double>((size_t)S);
+  return cv.ok;
+}
+
+// One select pass (sample -> bracket -> select): DEV = false
+// dst[c] = median_c(X[:, c]); DEV = true dst[c] = median_c(|X[:, c] - centre[c]|)
+template <bool DEV>
+static int select_pass(const double* X, int64_t R, int S, const double* centre, double* dst,
+                       const SelectBufs& b, hipStream_t s) {
   const int CB = S < BK_T ? S : BK_T;
   const int ctiles = (int)ceil_div(S, CB);
   // expected window keys per band 2 BR_MARG / SMP = 9% x 160 x 256 = 3680 <
@@ -389,36 +404,69 @@ int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
   // instead of whole 2-KB rows)
   const int64_t rpb = BK_ROWS;
   const unsigned nb = (unsigned)ceil_div(R, rpb);
-  for (int pass = 0; pass < 2; ++pass) {
-    const bool dev = pass == 1;
-    double* dst = dev ? out : med;
-    if (!dev) {
-      hipLaunchKernelGGL(col_sample_kernel<false>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S,
-                         (const double*)med, win, cnt);
-    } else {
-      hipLaunchKernelGGL(col_sample_kernel<true>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S,
-                         (const double*)med, win, cnt);
-    }
-    ABC_LAUNCHED();
-    if (!dev) {
-      hipLaunchKernelGGL(col_bracket_kernel<false>, dim3(nb, (unsigned)ctiles), dim3(BK_T), 0, s,
-                         X, R, S, (const double*)med, (const uint64_t*)win, rpb, cnt, scratch);
-    } else {
-      hipLaunchKernelGGL(col_bracket_kernel<true>, dim3(nb, (unsigned)ctiles), dim3(BK_T), 0, s,
-                         X, R, S, (const double*)med, (const uint64_t*)win, rpb, cnt, scratch);
-    }
-    ABC_LAUNCHED();
-    if (!dev) {
-      hipLaunchKernelGGL(col_select_kernel<false>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S,
-                         (const double*)med, (const unsigned long long*)cnt, (const uint64_t*)win,
-                         scratch, dst);
-    } else {
-      hipLaunchKernelGGL(col_select_kernel<true>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S,
-                         (const double*)med, (const unsigned long long*)cnt, (const uint64_t*)win,
-                         scratch, dst);
-    }
-    ABC_LAUNCHED();
-  }
+  hipLaunchKernelGGL(col_sample_kernel<DEV>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S, centre,
+                     b.win, b.cnt);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(col_bracket_kernel<DEV>, dim3(nb, (unsigned)ctiles), dim3(BK_T), 0, s, X, R,
+                     S, centre, (const uint64_t*)b.win, rpb, b.cnt, b.scratch);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(col_select_kernel<DEV>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S, centre,
+                     (const unsigned long long*)b.cnt, (const uint64_t*)b.win, b.scratch, dst);
+  ABC_LAUNCHED();
+  return ABC_OK;
+}
+
+// out[c] = median_c(|X[:, c] - median_c(X[:, c])|)
+int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
+                      size_t ws_bytes, hipStream_t s) {
+  Carver cv(ws, ws_bytes);
+  SelectBufs b;
+  if (!carve_select(cv, R, S, b)) return set_error(ABC_ERR_WORKSPACE, "column_mad: workspace carve");
+  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
+  if (rc) return rc;
+  return select_pass<true>(X, R, S, (const double*)b.med, out, b, s);
+}
+
+// out[c] = median_c(|X[:, c] - centre[c]|): one of the MAD's two passes
+int column_absdev_median_select(const double* X, int64_t R, int S, const double* centre,
+                                double* out, void* ws, size_t ws_bytes, hipStream_t s) {
+  Carver cv(ws, ws_bytes);
+  SelectBufs b;
+  if (!carve_select(cv, R, S, b))
+    return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace carve");
+  return select_pass<true>(X, R, S, centre, out, b, s);
+}
+
+namespace {
+__global__ void add_columns_kernel(const double* __restrict__ a, int S, double* __restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < S) out[c] = a[c] + out[c];
+}
+}  // namespace
+
+size_t select_cmad_ws_bytes(int64_t R, int S) {
+  size_t off = select_ws_bytes(R, S);
+  size_only<double>(off, (size_t)S);                   // the MAD beside the MAD to x0
+  return off + 256;
+}
+
+// out[c] = MAD_c + median_c(|X[:, c] - x0[c]|): three select passes, one add
+int column_cmad_select(const double* X, int64_t R, int S, const double* x0, double* out,
+                       void* ws, size_t ws_bytes, hipStream_t s) {
+  Carver cv(ws, ws_bytes);
+  SelectBufs b;
+  carve_select(cv, R, S, b);
+  double* mad = cv.take<double>((size_t)S);
+  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace carve");
+  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
+  if (rc) return rc;
+  rc = select_pass<true>(X, R, S, (const double*)b.med, mad, b, s);
+  if (rc) return rc;
+  rc = select_pass<true>(X, R, S, x0, out, b, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(add_columns_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s,
+                     (const double*)mad, S, out);
+  ABC_LAUNCHED();
   return ABC_OK;
 }
 

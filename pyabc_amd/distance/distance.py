@@ -9,7 +9,8 @@ Reference: pyabc/distance/distance.py
                                     :309-323, _bound_weights :325-348)
 Distances are evaluated by abc_pnorm over a device sum-stat matrix whose
 columns follow x_0's key order; the adaptive scales by abc_column_std /
-abc_column_mad over all recorded sum stats (accepted and rejected).
+abc_column_mad (abc_column_scale for the other eight scale functions of
+distance/scale.py) over all recorded sum stats (accepted and rejected).
 """
 import logging
 
@@ -193,7 +194,14 @@ class AdaptivePNormDistance(PNormDistance):
         else:
             mat = None
         if kern is not None and mat is not None:
-            col = gpu.column_std(mat) if kern == "std" else gpu.column_mad(mat)
+            if kern == "std":
+                col = gpu.column_std(mat)
+            elif kern == "mad":
+                col = gpu.column_mad(mat)
+            else:
+                # every other tagged function: x_0 in key order, one call
+                x0 = np.array([float(self.x_0[k]) for k in keys], dtype=np.float64)
+                col = gpu.column_scale(mat, kern, gpu.as_dev(x0, device=mat.device))
             return col.cpu().numpy()
         scales = []
         for key in keys:

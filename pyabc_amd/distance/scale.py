@@ -1,10 +1,16 @@
 """Scale functions for AdaptivePNormDistance (pyabc/distance/scale.py).
 
-``standard_deviation`` and ``median_absolute_deviation`` are the two the
-adaptive distance evaluates on the GPU over the recorded [R x S] sum-stat
-matrix (abc_column_std / abc_column_mad).  Called on a plain list (the
-reference signature ``f(data=list, x_0=float)``) they evaluate one column
-through the same kernels.
+The ten sum-stat scale functions (scale.py:38-135) carry a ``device_kernel``
+tag: the adaptive distance evaluates them on the GPU over the recorded
+[R x S] sum-stat matrix, all columns in one call (abc_column_std /
+abc_column_mad for ``standard_deviation`` / ``median_absolute_deviation``,
+abc_column_scale for the others; the tags are the keys of
+``_native.SCALE_KINDS``).  Called on a plain list (the reference signature
+``f(data=list, x_0=float)``) ``standard_deviation`` and
+``median_absolute_deviation`` evaluate one column through the same kernels
+and the other eight are the reference's numpy expressions.  ``span``,
+``mean`` and ``median`` (scales of the reference's AdaptiveAggregatedDistance)
+are untagged host functions.
 """
 import numpy as np
 
@@ -37,25 +43,46 @@ def mean_absolute_deviation(data, **kwargs):
     return np.mean(np.abs(data - np.mean(data)))
 
 
+mean_absolute_deviation.device_kernel = "mean_ad"
+
+
 def bias(data, x_0, **kwargs):
     return np.abs(np.mean(data) - x_0)
+
+
+bias.device_kernel = "bias"
 
 
 def root_mean_square_deviation(data, x_0, **kwargs):
     return np.sqrt(bias(data, x_0) ** 2 + np.std(data) ** 2)
 
 
+root_mean_square_deviation.device_kernel = "rmsd"
+
+
 def median_absolute_deviation_to_observation(data, x_0, **kwargs):
     return np.median(np.abs(np.array(data) - x_0))
+
+
+median_absolute_deviation_to_observation.device_kernel = "mad_to_obs"
 
 
 def mean_absolute_deviation_to_observation(data, x_0, **kwargs):
     return np.mean(np.abs(np.array(data) - x_0))
 
 
+mean_absolute_deviation_to_observation.device_kernel = "mean_ad_to_obs"
+
+
 def combined_median_absolute_deviation(data, x_0, **kwargs):
-    return (median_absolute_deviation(data)
+    # the MAD in numpy like its other half (the same bits as the select
+    # kernel's: both are exact order statistics)
+    data = np.array(data)
+    return (np.median(np.abs(data - np.median(data)))
             + median_absolute_deviation_to_observation(data, x_0))
+
+
+combined_median_absolute_deviation.device_kernel = "cmad"
 
 
 def combined_mean_absolute_deviation(data, x_0, **kwargs):
@@ -63,8 +90,14 @@ def combined_mean_absolute_deviation(data, x_0, **kwargs):
             + mean_absolute_deviation_to_observation(data, x_0))
 
 
+combined_mean_absolute_deviation.device_kernel = "cmean_ad"
+
+
 def standard_deviation_to_observation(data, x_0, **kwargs):
     return np.std(np.abs(np.array(data) - x_0))
+
+
+standard_deviation_to_observation.device_kernel = "std_to_obs"
 
 
 def span(data, **kwargs):

@@ -603,6 +603,22 @@ def column_mad(X):
     return out
 
 
+def column_scale(X, kind, x0=None):
+    """Scale function ``kind`` (a distance/scale.py ``device_kernel`` tag or
+    an ABC_SCALE_* value) of every column of X [R, S] against the observation
+    x0 [S] (device; not needed by "mad", "mean_ad", "std") -> [S] (device)."""
+    R, S = X.shape
+    kind = nat.SCALE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if x0 is not None and x0.numel() != S:
+        raise ValueError(f"column_scale: {x0.numel()} observations for {S} columns")
+    out = torch.empty(S, dtype=F64, device=X.device)
+    nb = nat.query("abc_column_scale_workspace", kind, R, S)
+    ws = workspace(nb, "colstats")
+    nat.call("abc_column_scale", kind, p(X), R, S, p(x0), p(out), p(ws),
+             ws.numel(), stream_ptr())
+    return out
+
+
 def bootstrap_cv(logdens, w, scale=1.0):
     """logdens [B, N] (bootstrapped log densities at N test points), w [N]
     -> (variation [N], cv [1]) on the device (abc_bootstrap_cv)."""

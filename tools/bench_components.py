@@ -10,7 +10,9 @@ peak.  Inputs are synthetic, generated on the device or from seeded numpy.
 
   c4        AdaptivePNormDistance on 256-dim summary stats, pop 2e5:
             pnorm over R candidates (R = 6.7e5 recorded at acceptance 0.3),
-            column std and MAD over the recorded [R x 256] matrix
+            column std and MAD over the recorded [R x 256] matrix; then
+            every abc_column_scale kind on that matrix, alternated with
+            column_std and column_mad round by round (ratio to them)
   quantile  QuantileEpsilon weighted quantile at N = 1e6 (c3) and 1e5 (c2)
   c5        LocalTransition d = 5, N = 1e5: k-NN covariance fit (k = 50 and
             the default k = N/4 = 25000), density of 1e5 candidates
@@ -90,6 +92,51 @@ def c4(reps):
     emit("column MAD (scale update)", "c4: [6.7e5 x 256] recorded", ms,
          bytes_=R * S * 8 * 2,
          extra={"note": "algorithmic = median pass + deviation pass, 8 B each"})
+    c4_scales(X, x0, reps)
+
+
+# abc_column_scale kinds: passes over X (8 R S bytes each), and the bound
+# relative to column_std / column_mad measured in the same rounds
+SCALE_PASSES = {"mean_ad": 2, "bias": 1, "rmsd": 2, "mad_to_obs": 1,
+                "mean_ad_to_obs": 1, "cmad": 3, "cmean_ad": 2, "std_to_obs": 2}
+SCALE_LIMIT = {"mean_ad": ("std", 1.25), "rmsd": ("std", 1.25),
+               "cmean_ad": ("std", 1.25), "std_to_obs": ("std", 1.25),
+               "bias": ("std", 0.75), "mean_ad_to_obs": ("std", 0.75),
+               "mad_to_obs": ("mad", 0.65), "cmad": ("mad", 1.65)}
+
+
+def c4_scales(X, x0, reps, inner=5):
+    """Every scale kind on the same matrix in one process: rounds of `inner`
+    calls each, column_std and column_mad timed in every round beside the
+    kinds (the same call, alternated); median and minimum over the rounds,
+    and the per-round ratio to the std / MAD of that round."""
+    from pyabc_amd import gpu
+    R, S = X.shape
+    fns = {"std": lambda: gpu.column_std(X), "mad": lambda: gpu.column_mad(X)}
+    for kind in SCALE_PASSES:
+        fns[kind] = (lambda k: lambda: gpu.column_scale(X, k, x0))(kind)
+    for kind in ("std", "mad"):      # the same bits through the new entry
+        fns["scale:" + kind] = (lambda k: lambda: gpu.column_scale(X, k, x0))(kind)
+    rounds = max(10, 2 * reps)
+    ms = {k: [] for k in fns}
+    for fn in fns.values():
+        fn()
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            ms[k].append(timed(fn, inner))
+    ms = {k: np.array(v) for k, v in ms.items()}
+    for k in fns:
+        base = k.split(":")[-1]
+        passes = SCALE_PASSES.get(base, 2)
+        extra = {"min_ms": round(float(ms[k].min()), 4), "rounds": rounds,
+                 "calls_per_round": inner, "passes": passes}
+        if base in SCALE_LIMIT:
+            ref, lim = SCALE_LIMIT[base]
+            ratio = float(np.median(ms[k] / ms[ref]))
+            extra.update({f"ratio_to_column_{ref}": round(ratio, 3), "limit": lim,
+                          "within_limit": bool(ratio <= lim)})
+        emit(f"column scale {k}", f"c4: [{R:.1e} x {S}] recorded, alternated",
+             float(np.median(ms[k])), bytes_=R * S * 8 * passes, extra=extra)
 
 
 def quantile(reps):
