@@ -14,8 +14,19 @@
  *     statistics in x_0 key order (pyabc/distance/distance.py:113-125).
  *   - `stream` is a hipStream_t (NULL = default stream).  Calls are
  *     stream-ordered and asynchronous unless stated; nothing allocates device
- *     memory inside a call: scratch comes from a caller workspace whose size
- *     the matching *_workspace() query returns.
+ *     memory inside a call.
+ *   - Workspace.  Scratch comes from a caller buffer (ws, ws_bytes).  An
+ *     entry describes its scratch once, as a layout of consecutive 256-byte
+ *     aligned regions; the entry carves that layout from (ws, ws_bytes) and
+ *     its *_workspace() query runs the same code without a buffer, so the
+ *     query's value is by construction what the entry carves (plus 256
+ *     trailing bytes) for the same shape arguments.  Queries are pure host
+ *     code and make no HIP call.  With ws_bytes below the query's value an
+ *     entry returns ABC_ERR_WORKSPACE before it enqueues or writes anything;
+ *     it never touches bytes past ws + ws_bytes.  Regions are aligned
+ *     relative to ws, so pass a 256-byte aligned ws (a torch allocation
+ *     is).  A workspace carries nothing from call to call except where
+ *     an entry says its first bytes must be zero before the first call.
  *   - Return 0 on success, a negative ABC_ERR_* code otherwise; the message is
  *     in abc_last_error() (thread-local).  No C++ exception crosses the ABI.
  */

@@ -54,23 +54,39 @@ int resident_blocks(K kernel, int block, int fallback = 1024) {
   return n;
 }
 
-// Carve consecutive 256-B aligned regions out of a caller workspace.
+// Carve consecutive 256-B aligned regions out of a caller workspace.  Every
+// entry's scratch is one layout: a struct of region pointers whose carve()
+// takes them from a Carver.  The launcher runs it over (ws, ws_bytes); the
+// size query runs the same carve() on a Carver without a base, which does the
+// same offset arithmetic, has no capacity and hands out null pointers.
 struct Carver {
-  char* base; size_t cap; size_t off = 0; bool ok = true;
-  Carver(void* b, size_t c) : base(static_cast<char*>(b)), cap(c) {}
+  static constexpr size_t SLACK = 256;   // every query's trailing bytes
+  uintptr_t base; size_t cap; size_t off = 0; bool ok = true;
+  Carver() : base(0), cap(SIZE_MAX) {}   // measuring
+  Carver(void* b, size_t c) : base(reinterpret_cast<uintptr_t>(b)), cap(c) {}
   template <class T> T* take(size_t n) {
     size_t start = align_up(off, 256);
     off = start + n * sizeof(T);
-    if (off > cap) ok = false;
-    return reinterpret_cast<T*>(base + start);
+    if (bytes() > cap) ok = false;
+    return base ? reinterpret_cast<T*>(base + start) : nullptr;
   }
-  // what is left after the pieces taken so far (256-byte aligned)
-  void* rest() const { return base + align_up(off, 256); }
-  size_t rest_bytes() const { return align_up(off, 256) < cap ? cap - align_up(off, 256) : 0; }
+  // what a workspace query returns; ok <=> cap >= bytes()
+  size_t bytes() const { return off + SLACK; }
 };
-template <class T> inline void size_only(size_t& off, size_t n) {
-  off = align_up(off, 256) + n * sizeof(T);
+// abc_X_workspace(shape): the bytes layout L carves for that shape
+template <class L, class... A> inline size_t measure(A... shape) {
+  Carver cv;
+  L w;
+  w.carve(cv, shape...);
+  return cv.bytes();
 }
+// a launcher's first step: carve layout w from its (ws, ws_bytes), or refuse
+#define ABC_CARVE(w, entry, ...)                                            \
+  do { ::abc::Carver cv_(ws, ws_bytes);                                     \
+       (w).carve(cv_, ##__VA_ARGS__);                                       \
+       if (!cv_.ok)                                                         \
+         return ::abc::set_error(ABC_ERR_WORKSPACE, entry ": workspace too small"); \
+  } while (0)
 
 // ---- Philox4x32-10 (oracle/philox.py restates this bit for bit) -----------
 struct u32x4 { uint32_t x, y, z, w; };

@@ -59,9 +59,14 @@ __global__ void cv_final_kernel(const double* __restrict__ part, int nblk,
 
 using namespace abc;
 
+struct CvWs {
+  double* part;   // per-block partial sums
+  void carve(Carver& c) { part = c.take<double>(CV_BLOCKS); }
+};
+
 extern "C" size_t abc_bootstrap_cv_workspace(int64_t N) {
   (void)N;
-  return sizeof(double) * CV_BLOCKS + 256;
+  return measure<CvWs>();
 }
 
 extern "C" int abc_bootstrap_cv(const double* logdens, int64_t B, int64_t N,
@@ -71,11 +76,11 @@ extern "C" int abc_bootstrap_cv(const double* logdens, int64_t B, int64_t N,
   ABC_CHECK_ARG(B >= 1 && N >= 1, "bootstrap_cv: B < 1 or N < 1");
   ABC_CHECK_ARG(logdens && w && variation && cv && ws,
                 "bootstrap_cv: null pointer");
-  if (ws_bytes < abc_bootstrap_cv_workspace(N))
-    return set_error(ABC_ERR_WORKSPACE, "bootstrap_cv: workspace too small");
+  CvWs wk;
+  ABC_CARVE(wk, "bootstrap_cv");
   hipStream_t s = as_stream(stream);
   const int nblk = (int)(ceil_div(N, 256) < CV_BLOCKS ? ceil_div(N, 256) : CV_BLOCKS);
-  double* part = static_cast<double*>(ws);
+  double* part = wk.part;
   hipLaunchKernelGGL(cv_column_kernel, dim3(nblk), dim3(256), 0, s, logdens, B,
                      N, w, scale, variation, part);
   ABC_LAUNCHED();

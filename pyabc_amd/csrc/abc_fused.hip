@@ -879,27 +879,16 @@ using namespace abc;
 // workspace: tile ticket (zero before the first call; every round leaves it
 // zero) | range totals | prior support box | accept bits
 struct RoundWs {
-  unsigned int* ticket; int64_t* rtot; double* box; uint64_t* bits; bool ok;
+  unsigned int* ticket; int64_t* rtot; double* box; uint64_t* bits;
+  void carve(Carver& c, int64_t B) {
+    ticket = c.take<unsigned int>(64);
+    rtot = c.take<int64_t>(RG_MAX);
+    box = c.take<double>(128);
+    bits = c.take<uint64_t>((size_t)ceil_div(B > 0 ? B : 1, FR_TILE) * FR_WORDS);
+  }
 };
-inline RoundWs carve_round_ws(void* ws, size_t ws_bytes, int64_t B) {
-  Carver c(ws, ws_bytes);
-  RoundWs w;
-  w.ticket = c.take<unsigned int>(64);
-  w.rtot = c.take<int64_t>(RG_MAX);
-  w.box = c.take<double>(128);
-  w.bits = c.take<uint64_t>((size_t)ceil_div(B > 0 ? B : 1, FR_TILE) * FR_WORDS);
-  w.ok = c.ok;
-  return w;
-}
 
-extern "C" size_t abc_candidates_workspace(int64_t B) {
-  size_t off = 0;
-  size_only<unsigned int>(off, 64);
-  size_only<int64_t>(off, RG_MAX);
-  size_only<double>(off, 128);
-  size_only<uint64_t>(off, (size_t)ceil_div(B > 0 ? B : 1, FR_TILE) * FR_WORDS);
-  return off + 256;
-}
+extern "C" size_t abc_candidates_workspace(int64_t B) { return measure<RoundWs>(B); }
 
 extern "C" int64_t abc_ancestor_table_bytes(int64_t N, int d) {
   if (N < 1 || d < 1) return 0;
@@ -942,8 +931,8 @@ extern "C" int abc_candidates_round(const abc_candidate_spec* spec, int64_t idx0
   ABC_CHECK_ARG(B >= 0 && cap >= 0 && count, "candidates_round: bad B/cap/count");
   ABC_CHECK_ARG(B < (1ll << 40), "candidates_round: B too large");
   ABC_CHECK_ARG(cap == 0 || idx, "candidates_round: null idx");
-  if (ws_bytes < abc_candidates_workspace(B))
-    return set_error(ABC_ERR_WORKSPACE, "candidates_round: workspace too small");
+  RoundWs w;
+  ABC_CARVE(w, "candidates_round", B);
   hipStream_t s = as_stream(stream);
   if (B == 0) {
     ABC_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
@@ -956,8 +945,6 @@ extern "C" int abc_candidates_round(const abc_candidate_spec* spec, int64_t idx0
                     (p == 1.0 || p == 2.0 || p == INFINITY)) ? 1 : 0;
   const int64_t nt = ceil_div(B, FR_TILE);
   ABC_CHECK_ARG(nt < (1ll << 31), "candidates_round: too many tiles");
-  const RoundWs w = carve_round_ws(ws, ws_bytes, B);
-  if (!w.ok) return set_error(ABC_ERR_WORKSPACE, "candidates_round: workspace");
   const double* box = spec->support_box;
   if (!box) {
     hipLaunchKernelGGL(support_box_kernel, dim3((unsigned)spec->d), dim3(64), 0, s,
@@ -983,8 +970,8 @@ extern "C" int abc_pnorm_accept(const double* x, int64_t B, int S, const double*
   ABC_CHECK_ARG(S >= 1 && B >= 0 && p >= 1.0 && cap >= 0, "pnorm_accept: bad S/B/p/cap");
   ABC_CHECK_ARG(B < (1ll << 40), "pnorm_accept: B too large");
   ABC_CHECK_ARG(count && (cap == 0 || idx), "pnorm_accept: null pointer");
-  if (ws_bytes < abc_candidates_workspace(B))
-    return set_error(ABC_ERR_WORKSPACE, "pnorm_accept: workspace too small");
+  RoundWs w;
+  ABC_CARVE(w, "pnorm_accept", B);
   hipStream_t s = as_stream(stream);
   if (B == 0) {
     ABC_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
@@ -993,8 +980,6 @@ extern "C" int abc_pnorm_accept(const double* x, int64_t B, int S, const double*
   ABC_CHECK_ARG(x && x0 && wf, "pnorm_accept: null pointer");
   const int64_t nt = ceil_div(B, FR_TILE);
   ABC_CHECK_ARG(nt < (1ll << 31), "pnorm_accept: too many tiles");
-  const RoundWs w = carve_round_ws(ws, ws_bytes, B);
-  if (!w.ok) return set_error(ABC_ERR_WORKSPACE, "pnorm_accept: workspace");
   uint64_t* bits = w.bits;
   // the same row / wave split as abc_pnorm (the same bits per row)
   if (S <= 32)
@@ -1028,7 +1013,12 @@ extern "C" int abc_round_keep(const int64_t* counts, int nranks, int rank, int64
   return ABC_OK;
 }
 
-extern "C" size_t abc_candidates_propose_workspace() { return 128 * sizeof(double) + 256; }
+struct ProposeWs {
+  double* box;
+  void carve(Carver& c) { box = c.take<double>(128); }
+};
+
+extern "C" size_t abc_candidates_propose_workspace() { return measure<ProposeWs>(); }
 
 extern "C" int abc_candidates_propose(const abc_candidate_spec* spec, int64_t idx0, int64_t B,
                                       double* theta, double* prior_logpdf, int64_t* ancestor,
@@ -1039,11 +1029,10 @@ extern "C" int abc_candidates_propose(const abc_candidate_spec* spec, int64_t id
   ABC_CHECK_ARG(B >= 0 && B < (1ll << 40), "candidates_propose: bad B");
   if (B == 0) return ABC_OK;
   ABC_CHECK_ARG(theta, "candidates_propose: null pointer");
-  if (ws_bytes < abc_candidates_propose_workspace())
-    return set_error(ABC_ERR_WORKSPACE, "candidates_propose: workspace too small");
+  ProposeWs w;
+  ABC_CARVE(w, "candidates_propose");
   hipStream_t s = as_stream(stream);
-  Carver c(ws, ws_bytes);
-  double* box = c.take<double>(128);
+  double* box = w.box;
   if (spec->support_box) {
     box = const_cast<double*>(spec->support_box);
   } else {

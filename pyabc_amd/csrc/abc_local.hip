@@ -1112,18 +1112,64 @@ void launch_moments(const double* X, const float* X32, const double* M, const do
     launch_moments<D, SL + 1>(X, X32, M, w, N, sel_v, sel_ties, sel_rank0, part, RS, s, done);
 }
 
+// launch_fit's workspace, from (N, D) alone: every region of every path, each
+// at its largest, in the order the paths use them
+template <int D>
+struct FitWs {
+  unsigned long long* sel_v; long long* sel_ties; long long* sel_rank0; float* X32; double* Mx;
+  // fp32-MFMA k-NN select (abc_local_knn.h)
+  double* cen; float* knn_img; unsigned long long* r2; int* need; int* done; int* cnt;
+  double* lmom;
+  double* part;   // partial moments of the row chunks (local_moments_kernel)
+  // dense-neighbourhood MFMA path (D <= 5, abc_local_dense.h)
+  unsigned long long* bnd; int* flag; int* qcnt; int* cbelow; int* qidx; half8* img;
+  double* part16; double* cenm; float* drows;
+  void carve(Carver& cv, int64_t N) {
+    constexpr size_t NM = local_nm<D>();
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    sel_v = cv.take<unsigned long long>(n);
+    sel_ties = cv.take<long long>(n);            // index cutoff of the ties
+    sel_rank0 = cv.take<long long>(n);
+    X32 = cv.take<float>(n * D);                 // fp32 prefilter copy
+    Mx = cv.take<double>(1);                     // max |X|
+    cen = cv.take<double>(D);
+    knn_img = cv.take<float>((size_t)(ceil_div(n, 16) + KN_PAD) * kn_kb<D>() * 64);  // + prefetch padding
+    r2 = cv.take<unsigned long long>(1);
+    need = cv.take<int>(n);
+    done = cv.take<int>(n);
+    cnt = cv.take<int>(2);
+    lmom = cv.take<double>(kn_list_capable<D>() ? NM * n : 1);
+    // (>= 2 NM N: the dense path's deferred collect keeps its member sums and
+    // their rounding bounds there)
+    const int RS = moments_chunks(n);
+    part = cv.take<double>((size_t)(RS < 2 ? 2 : RS) * NM * n);
+    if constexpr (D <= 5) {
+      const int64_t nsteps = ceil_div(n, 32);
+      bnd = cv.take<unsigned long long>(1 + D);
+      flag = cv.take<int>(2);                    // [rounding bound missed, deferred-collect failures]
+      qcnt = cv.take<int>(n);                    // deferred collect: queue lengths
+      cbelow = cv.take<int>(n);                  //   certain-below counts
+      qidx = cv.take<int>(n * KN_QCAP);          //   queued rows
+      // (+ DM_SB steps: knn_dense_kernel's stage loads past the last step)
+      img = cv.take<half8>((size_t)(nsteps + DM_SB) * mm_nt<D>() * 64);
+      part16 = cv.take<double>((size_t)mm_chunks(n, nsteps) * 16 * mm_nt<D>() * n);
+      cenm = cv.take<double>(NM * n);
+      drows = cv.take<float>((size_t)(nsteps + DM_SB) * dm_rstep<D>());
+    }
+  }
+};
+
 template <int D>
 int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                double scaling, double eps, double* covs, double* inv,
                double* dets, double* chol, double* lnorm, void* ws,
                size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  unsigned long long* sel_v = cv.take<unsigned long long>((size_t)N);
-  long long* sel_ties = cv.take<long long>((size_t)N);  // index cutoff of the ties
-  long long* sel_rank0 = cv.take<long long>((size_t)N);
-  float* X32 = cv.take<float>((size_t)N * D);              // fp32 prefilter copy
-  double* Mx = cv.take<double>(1);                          // max |X|
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "local_fit: workspace too small");
+  FitWs<D> k;
+  ABC_CARVE(k, "local_fit", N);
+  unsigned long long* sel_v = k.sel_v;
+  long long *sel_ties = k.sel_ties, *sel_rank0 = k.sel_rank0;
+  float* X32 = k.X32;
+  double* Mx = k.Mx;
   ABC_HIP(hipMemsetAsync(Mx, 0, sizeof(double), s));
   {
     const int64_t nx = N * D;
@@ -1132,7 +1178,6 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                        reinterpret_cast<unsigned long long*>(Mx));
     ABC_LAUNCHED();
   }
-  constexpr int NM = local_nm<D>();
   // k-NN selection on fp32 MFMA keys (abc_local_knn.h) for N >= KN_MIN_N;
   // small k sums the moments in the same kernel (list mode)
   const bool knn = N >= KN_MIN_N;
@@ -1143,24 +1188,16 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
   // dense k after the k-NN select's count sweep: the moments sweep does the
   // collect (deferred collect, abc_local_dense.h) -- one sweep less
   const bool defer = knn && !list_ok && dense;
-  int* done = nullptr;
-  double* lmom = nullptr;
-  double* cen = nullptr;
-  unsigned long long* r2 = nullptr;
+  // (null without the k-NN select, as the kernels below expect)
+  int* done = knn ? k.done : nullptr;
+  double* lmom = knn ? k.lmom : nullptr;
+  double* cen = knn ? k.cen : nullptr;
+  unsigned long long* r2 = knn ? k.r2 : nullptr;
   int h_cnt[2] = {0, 0};
-  int* knn_need = nullptr;
-  int* knn_cnt = nullptr;
-  float* knn_img = nullptr;
   if (knn) {
     const int64_t nt = ceil_div(N, 16) + KN_PAD;   // + prefetch padding
-    cen = cv.take<double>(D);
-    float* img = cv.take<float>((size_t)nt * kn_kb<D>() * 64);
-    r2 = cv.take<unsigned long long>(1);
-    int* need = cv.take<int>((size_t)N);
-    done = cv.take<int>((size_t)N);
-    int* cnt = cv.take<int>(2);
-    lmom = cv.take<double>(kn_list_capable<D>() ? (size_t)NM * N : 1);
-    if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "local_fit: workspace too small");
+    float* img = k.knn_img;
+    int *need = k.need, *cnt = k.cnt;
     ABC_HIP(hipMemsetAsync(r2, 0, sizeof(unsigned long long), s));
     ABC_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(int), s));
     hipLaunchKernelGGL((knn_center_kernel<D>), dim3(1), dim3(1024), 0, s, X, N, cen);
@@ -1168,9 +1205,6 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
     hipLaunchKernelGGL((knn_prep_kernel<D>), dim3((unsigned)ceil_div(nt * 16, 256)), dim3(256), 0,
                        s, X, N, (const double*)cen, img, r2);
     ABC_LAUNCHED();
-    knn_need = need;
-    knn_img = img;
-    knn_cnt = cnt;
     hipLaunchKernelGGL((knn_select_kernel<D>), dim3((unsigned)ceil_div(N, KN_PB)), dim3(256), 0,
                        s, X, w, N, nq, (const double*)cen, (const float*)img,
                        (const double*)r2, (int)list_ok, (int)defer, sel_v, sel_ties, sel_rank0,
@@ -1196,26 +1230,17 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
   }
   const bool all_listed = list_ok && h_cnt[1] == N;
   const int RS = N > 1 ? moments_chunks(N) : 1;
-  // (>= 2 NM N: the dense path's deferred collect keeps its member sums and
-  // their rounding bounds there)
-  double* part = cv.take<double>(all_listed ? 1 : (size_t)(RS < 2 ? 2 : RS) * NM * (size_t)N);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "local_fit: workspace too small");
+  double* part = k.part;
   const double* mom = part;
   int mom_rs = RS;
   if constexpr (D <= 5) if (dense) {
     const int64_t nsteps = ceil_div(N, 32);
     const int RS16 = mm_chunks(N, nsteps);
-    unsigned long long* bnd = cv.take<unsigned long long>(1 + D);
-    int* flag = cv.take<int>(2);            // [rounding bound missed, deferred-collect failures]
-    int* qcnt = cv.take<int>((size_t)N);
-    int* cbelow = cv.take<int>((size_t)N);
-    int* qidx = cv.take<int>((size_t)N * KN_QCAP);
-    // (+ DM_SB steps: knn_dense_kernel's stage loads past the last step)
-    half8* img = cv.take<half8>((size_t)(nsteps + DM_SB) * mm_nt<D>() * 64);
-    double* part16 = cv.take<double>((size_t)RS16 * 16 * mm_nt<D>() * (size_t)N);
-    double* cenm = cv.take<double>((size_t)NM * N);
-    float* drows = cv.take<float>((size_t)(nsteps + DM_SB) * dm_rstep<D>());
-    if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "local_fit: workspace too small");
+    unsigned long long* bnd = k.bnd;
+    int *flag = k.flag, *qcnt = k.qcnt, *cbelow = k.cbelow, *qidx = k.qidx;
+    half8* img = k.img;
+    double *part16 = k.part16, *cenm = k.cenm;
+    float* drows = k.drows;
     ABC_HIP(hipMemsetAsync(bnd, 0, sizeof(unsigned long long) * (1 + D), s));
     ABC_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), s));
     const int64_t bb = ceil_div(N, 256) < 256 ? ceil_div(N, 256) : 256;
@@ -1243,7 +1268,7 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                            (const long long*)sel_rank0, part16, qcnt, qidx, cbelow);
         ABC_LAUNCHED();
         hipLaunchKernelGGL((knn_resolve_kernel<D>), dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, s,
-                           X, w, N, nq, (const int*)knn_need, sel_v, sel_ties, sel_rank0,
+                           X, w, N, nq, (const int*)k.need, sel_v, sel_ties, sel_rank0,
                            (const int*)qcnt, (const int*)qidx, (const int*)cbelow,
                            (const double*)bnd, part16, part, flag + 1);
         ABC_LAUNCHED();
@@ -1258,16 +1283,16 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
           // some particle's bracket or queue failed: the select with its own
           // collect sweep (and the fp64 radix select behind it), then the
           // plain moments sweep
-          ABC_HIP(hipMemsetAsync(knn_cnt, 0, 2 * sizeof(int), s));
+          ABC_HIP(hipMemsetAsync(k.cnt, 0, 2 * sizeof(int), s));
           ABC_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), s));
           hipLaunchKernelGGL((knn_select_kernel<D>), dim3((unsigned)ceil_div(N, KN_PB)), dim3(256),
-                             0, s, X, w, N, nq, (const double*)cen, (const float*)knn_img,
-                             (const double*)r2, 0, 0, sel_v, sel_ties, sel_rank0, knn_need,
-                             done, lmom, knn_cnt);
+                             0, s, X, w, N, nq, (const double*)cen, (const float*)k.knn_img,
+                             (const double*)r2, 0, 0, sel_v, sel_ties, sel_rank0, k.need,
+                             done, lmom, k.cnt);
           ABC_LAUNCHED();
           hipLaunchKernelGGL((local_select_kernel<D, sel_pb<D>()>),
                              dim3((unsigned)ceil_div(N, sel_pb<D>())), dim3(256), 0, s, X, N, nq,
-                             sel_v, sel_ties, sel_rank0, (const int*)knn_need);
+                             sel_v, sel_ties, sel_rank0, (const int*)k.need);
           ABC_LAUNCHED();
           plain = true;
         } else {
@@ -1520,37 +1545,44 @@ __global__ __launch_bounds__(256) void local_combine_kernel(
   out[i] = (l > 0.0) ? LN2_L * (m + log2(l)) - log(wsum[0]) : -INFINITY;
 }
 
+// population tiles and their chunks (the launch grid's y)
 template <int D>
-size_t pdf_workspace(int64_t M, int64_t N, int* nchunks_out) {
-  const int64_t ntiles = ceil_div(N, 16);
-  const int64_t cblocks = ceil_div(M > 0 ? M : 1, 4 * LocalFeat<D>::NT * 16);
-  // enough workgroups for 256 CUs x several waves, chunks of >= 64 tiles
-  int64_t nch = ceil_div(4096, cblocks);   // ~4096 blocks (A/B at c5: 2048 -> 4096 10.0 -> 9.2 ms; 1024, 8192, 16384 slower)
-  nch = nch < 1 ? 1 : nch;
-  const int64_t maxch = ceil_div(ntiles, 64);
-  nch = nch > maxch ? maxch : nch;
-  nch = nch > 64 ? 64 : nch;
-  if (nchunks_out) *nchunks_out = (int)nch;
-  size_t off = 0;
-  size_only<double>(off, (size_t)ntiles * LocalFeat<D>::KB * 64);
-  size_only<double2>(off, (size_t)nch * (M > 0 ? M : 1));
-  size_only<double>(off, 1);
-  return off + 256;
-}
+struct PdfPlan {
+  int64_t ntiles; int nch;
+  PdfPlan() = default;
+  PdfPlan(int64_t M, int64_t N) {
+    ntiles = ceil_div(N, 16);
+    const int64_t cblocks = ceil_div(M > 0 ? M : 1, 4 * LocalFeat<D>::NT * 16);
+    // enough workgroups for 256 CUs x several waves, chunks of >= 64 tiles
+    int64_t n = ceil_div(4096, cblocks);   // ~4096 blocks (A/B at c5: 2048 -> 4096 10.0 -> 9.2 ms; 1024, 8192, 16384 slower)
+    n = n < 1 ? 1 : n;
+    const int64_t maxch = ceil_div(ntiles, 64);
+    n = n > maxch ? maxch : n;
+    nch = (int)(n > 64 ? 64 : n);
+  }
+};
+
+template <int D>
+struct PdfWs {
+  PdfPlan<D> p; double* psi; double2* part; double* wsum;
+  void carve(Carver& c, int64_t M, int64_t N) {
+    p = PdfPlan<D>(M, N);
+    psi = c.take<double>((size_t)p.ntiles * LocalFeat<D>::KB * 64);
+    part = c.take<double2>((size_t)p.nch * (M > 0 ? M : 1));
+    wsum = c.take<double>(1);
+  }
+};
 
 template <int D>
 int launch_pdf(const double* x, int64_t M, const double* X, const double* w,
                int64_t N, const double* inv, const double* lnorm, double* out,
                void* ws, size_t ws_bytes, hipStream_t s) {
-  int nch = 1;
-  if (ws_bytes < pdf_workspace<D>(M, N, &nch))
-    return set_error(ABC_ERR_WORKSPACE, "local_logpdf: workspace too small");
-  const int64_t ntiles = ceil_div(N, 16);
+  PdfWs<D> k;
+  ABC_CARVE(k, "local_logpdf", M, N);
+  auto [plan, psi, part, wsum] = k;
+  const int nch = plan.nch;
+  const int64_t ntiles = plan.ntiles;
   constexpr int KB = LocalFeat<D>::KB, NT = LocalFeat<D>::NT;
-  Carver c(ws, ws_bytes);
-  double* psi = c.take<double>((size_t)ntiles * KB * 64);
-  double2* part = c.take<double2>((size_t)nch * M);
-  double* wsum = c.take<double>(1);
   const int64_t npack = ntiles * KB * 64;
   hipLaunchKernelGGL(local_pack_kernel<D>, dim3((unsigned)ceil_div(npack, 256)), dim3(256), 0,
                      s, X, w, inv, lnorm, N, ntiles, psi);
@@ -1584,42 +1616,13 @@ using namespace abc;
 
 extern "C" size_t abc_local_fit_workspace(int64_t N, int d) {
   if (d > 16) return local_wide_fit_workspace(N, d);
-  size_t off = 0;
-  for (int i = 0; i < 3; ++i) size_only<int64_t>(off, (size_t)(N > 0 ? N : 1));
-  size_only<float>(off, (size_t)(N > 0 ? N : 1) * (size_t)d);   // X32
-  size_only<double>(off, 1);                                     // max |X|
-  // partial moments of the row chunks (local_moments_kernel)
-  const size_t nm = 2 + (size_t)d + (size_t)d * (d + 1) / 2;
-  {
-    const int rs = moments_chunks(N > 1 ? N : 1);
-    size_only<double>(off, (size_t)(rs < 2 ? 2 : rs) * nm * (size_t)(N > 0 ? N : 1));
+  switch (d) {
+#define ABC_D(n) case n: return measure<FitWs<n>>(N);
+    ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
+    ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
+#undef ABC_D
   }
-  {  // fp32-MFMA k-NN select (abc_local_knn.h)
-    const int64_t n1 = N > 0 ? N : 1;
-    const int64_t nt = (n1 + 15) / 16;
-    size_only<double>(off, (size_t)d);
-    size_only<float>(off, (size_t)(nt + KN_PAD) * ((d + 5) / 4) * 64);   // + prefetch padding
-    size_only<unsigned long long>(off, 1);
-    size_only<int>(off, (size_t)n1);
-    size_only<int>(off, (size_t)n1);
-    size_only<int>(off, 2);
-    size_only<double>(off, nm * (size_t)n1);
-  }
-  if (d <= 5) {   // dense-neighbourhood MFMA path (mm_*_kernel)
-    const int64_t n1 = N > 0 ? N : 1;
-    const int64_t nsteps = (n1 + 31) / 32;
-    const int64_t nt = ((int64_t)nm * ML_NL + 15) / 16;
-    size_only<unsigned long long>(off, 1 + (size_t)d);
-    size_only<int>(off, 2);
-    size_only<int>(off, (size_t)n1);                 // deferred collect: queue lengths
-    size_only<int>(off, (size_t)n1);                 //   certain-below counts
-    size_only<int>(off, (size_t)n1 * KN_QCAP);       //   queued rows
-    size_only<half8>(off, (size_t)((nsteps + DM_SB) * nt * 64));
-    size_only<double>(off, (size_t)mm_chunks(n1, nsteps) * 16 * nt * (size_t)n1);
-    size_only<double>(off, nm * (size_t)n1);
-    size_only<float>(off, (size_t)(nsteps + DM_SB) * dm_rstep<5>());
-  }
-  return off + 256;
+  return Carver::SLACK;
 }
 
 extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
@@ -1629,7 +1632,7 @@ extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
                              size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(N >= 1 && d >= 1 && d <= ABC_MAX_D && k >= 1, "local_fit: bad N/d/k");
   ABC_CHECK_ARG(N < (1ll << 31), "local_fit: N >= 2^31");
-  ABC_CHECK_ARG(ws && ws_bytes >= abc_local_fit_workspace(N, d), "local_fit: workspace");
+  ABC_CHECK_ARG(ws, "local_fit: workspace");
   ABC_CHECK_ARG(X && w && covs && inv_covs && dets && chol && log_norm, "local_fit: null pointer");
   const int64_t nq = (k + 1) < N ? (k + 1) : N;
   hipStream_t s = as_stream(stream);
@@ -1647,12 +1650,12 @@ extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
 
 extern "C" size_t abc_local_logpdf_workspace(int64_t M, int64_t N, int d) {
   switch (d) {
-#define ABC_D(n) case n: return pdf_workspace<n>(M, N, nullptr);
+#define ABC_D(n) case n: return measure<PdfWs<n>>(M, N);
     ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
     ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
 #undef ABC_D
   }
-  return 256;
+  return Carver::SLACK;
 }
 
 extern "C" int abc_local_logpdf(const double* x, int64_t M, const double* X,

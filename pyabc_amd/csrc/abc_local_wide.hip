@@ -482,34 +482,32 @@ int wide_fit_blocks(int64_t N, int d) {
 
 }  // namespace
 
-size_t local_wide_fit_workspace(int64_t N, int d) {
-  const int64_t n1 = N > 0 ? N : 1;
-  const int g = wide_fit_blocks(n1, d);
-  size_t off = 0;
-  size_only<unsigned long long>(off, (size_t)g * n1);
-  size_only<int32_t>(off, (size_t)g * n1);
-  if (d > WD_MAX) size_only<double>(off, (size_t)g * wide_big_doubles(d));
-  return off + 256;
-}
+// per workgroup: keys | member list | (d > WD_MAX) the big matrices
+struct WideFitWs {
+  int g; unsigned long long* keys; int32_t* members; double* big;
+  void carve(Carver& c, int64_t N, int d) {
+    const int64_t n1 = N > 0 ? N : 1;
+    g = wide_fit_blocks(n1, d);
+    keys = c.take<unsigned long long>((size_t)g * n1);
+    members = c.take<int32_t>((size_t)g * n1);
+    big = d > WD_MAX ? c.take<double>((size_t)g * wide_big_doubles(d)) : nullptr;
+  }
+};
+
+size_t local_wide_fit_workspace(int64_t N, int d) { return measure<WideFitWs>(N, d); }
 
 int local_wide_fit(const double* X, const double* w, int64_t N, int d, int64_t nq,
                    double scaling, double eps, double* covs, double* invs, double* dets,
                    double* chol, double* lnorm, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (ws_bytes < local_wide_fit_workspace(N, d))
-    return set_error(ABC_ERR_WORKSPACE, "local_fit (d > 16): workspace too small");
-  const int g = wide_fit_blocks(N, d);
-  Carver c(ws, ws_bytes);
-  WideFitArgs A{X, w, N, d, nq, scaling, eps, nullptr, nullptr,
-                covs, invs, dets, chol, lnorm, nullptr};
-  A.keys = c.take<unsigned long long>((size_t)g * N);
-  A.members = c.take<int32_t>((size_t)g * N);
-  if (d > WD_MAX) {
-    A.big = c.take<double>((size_t)g * wide_big_doubles(d));
-    if (!c.ok) return set_error(ABC_ERR_WORKSPACE, "local_fit (d > 64): workspace carve");
+  WideFitWs k;
+  ABC_CARVE(k, "local_fit (d > 16)", N, d);
+  const int g = k.g;
+  WideFitArgs A{X, w, N, d, nq, scaling, eps, k.keys, k.members,
+                covs, invs, dets, chol, lnorm, k.big};
+  if (d > WD_MAX)
     hipLaunchKernelGGL(local_wide_fit_kernel<true>, dim3((unsigned)g), dim3(WT), 0, s, A);
-  } else {
+  else
     hipLaunchKernelGGL(local_wide_fit_kernel<false>, dim3((unsigned)g), dim3(WT), 0, s, A);
-  }
   ABC_LAUNCHED();
   return ABC_OK;
 }

@@ -403,15 +403,16 @@ Plan make_plan(int64_t M, int64_t N, int r, int prec) {
   return p;
 }
 
-size_t plan_ws(const Plan& p) {
-  size_t off = 0;
-  if (p.esize == 4) size_only<float>(off, (size_t)p.MTpad * 64 * p.KB);
-  else size_only<double>(off, (size_t)p.MTpad * 64 * p.KB);
-  size_only<double>(off, (size_t)p.Mpad);                      // m0
-  size_only<double>(off, (size_t)p.nchunk * p.Mpad);           // part m
-  size_only<double>(off, (size_t)p.nchunk * p.Mpad);           // part l
-  return off + 256;
-}
+struct PlanWs {
+  void* Bp; double* m0; double* pm; double* pl;
+  void carve(Carver& cv, const Plan& p) {
+    Bp = (p.esize == 4) ? (void*)cv.take<float>((size_t)p.MTpad * 64 * p.KB)
+                        : (void*)cv.take<double>((size_t)p.MTpad * 64 * p.KB);
+    m0 = cv.take<double>((size_t)p.Mpad);
+    pm = cv.take<double>((size_t)p.nchunk * p.Mpad);   // part m
+    pl = cv.take<double>((size_t)p.nchunk * p.Mpad);   // part l
+  }
+};
 
 template <class T, int KB>
 void launch_lse(const Plan& p, const T* A, const T* B, const double* m0,
@@ -499,7 +500,7 @@ extern "C" int abc_mvn_pack_population(const double* X, const double* w,
 
 extern "C" size_t abc_mvn_logpdf_workspace(int64_t M, int64_t N, int r, int prec) {
   if (prec == ABC_PREC_X3) return x3_logpdf_workspace(M, N, r);
-  return plan_ws(make_plan(M, N, r, prec));
+  return measure<PlanWs>(make_plan(M, N, r, prec));
 }
 
 extern "C" int abc_mvn_logpdf(const double* x, int64_t M, int d,
@@ -520,16 +521,10 @@ extern "C" int abc_mvn_logpdf(const double* x, int64_t M, int d,
                      log_const + log_w_shift, out, hint_rows, ws, ws_bytes,
                      as_stream(stream));
   Plan p = make_plan(M, N, r, prec);
-  if (ws_bytes < plan_ws(p))
-    return set_error(ABC_ERR_WORKSPACE, "logpdf: workspace %zu < %zu", ws_bytes, plan_ws(p));
+  PlanWs k;
+  ABC_CARVE(k, "logpdf", p);
   hipStream_t s = as_stream(stream);
-  Carver cv(ws, ws_bytes);
-  void* Bp = (p.esize == 4) ? (void*)cv.take<float>((size_t)p.MTpad * 64 * p.KB)
-                            : (void*)cv.take<double>((size_t)p.MTpad * 64 * p.KB);
-  double* m0 = cv.take<double>((size_t)p.Mpad);
-  double* pm = cv.take<double>((size_t)p.nchunk * p.Mpad);
-  double* pl = cv.take<double>((size_t)p.nchunk * p.Mpad);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "logpdf: workspace carve");
+  auto [Bp, m0, pm, pl] = k;
   dim3 gB((unsigned)ceil_div(p.MTpad * 16, 128)), bB(128);
   int rc;
   if (p.esize == 4) {

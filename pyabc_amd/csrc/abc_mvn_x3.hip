@@ -934,17 +934,19 @@ PlanX3 make_plan_x3(int64_t M, int64_t N, int r, bool fine = false) {
   return p;
 }
 
-size_t plan_x3_ws(const PlanX3& p) {
-  size_t off = 0;
-  size_only<_Float16>(off, (size_t)p.MTpad * p.KB * 64 * 8);  // candidate image
-  size_only<int32_t>(off, (size_t)p.Mpad);                     // candidate flags
-  size_only<float>(off, (size_t)p.Mpad);                       // hinted offsets
-  size_only<double>(off, (size_t)p.nchunk * p.Mpad);           // partial offsets
-  size_only<double>(off, (size_t)p.nchunk * p.Mpad);           // partial sums
-  size_only<int64_t>(off, (size_t)p.Mpad);                     // rescue list
-  size_only<unsigned int>(off, 64);                            // rescue count
-  return off + 256;
-}
+struct X3PlanWs {
+  _Float16* Bimg; int32_t* cflags; float* cand_o; double* po; double* pl;
+  int64_t* rescue; unsigned int* nres;
+  void carve(Carver& cv, const PlanX3& p) {
+    Bimg = cv.take<_Float16>((size_t)p.MTpad * p.KB * 64 * 8);  // candidate image
+    cflags = cv.take<int32_t>((size_t)p.Mpad);                   // candidate flags
+    cand_o = cv.take<float>((size_t)p.Mpad);                     // hinted offsets
+    po = cv.take<double>((size_t)p.nchunk * p.Mpad);             // partial offsets
+    pl = cv.take<double>((size_t)p.nchunk * p.Mpad);             // partial sums
+    rescue = cv.take<int64_t>((size_t)p.Mpad);                   // rescue list
+    nres = cv.take<unsigned int>(64);                            // rescue count
+  }
+};
 
 template <int KB, int CT>
 void launch_x3(const PlanX3& p, const half8* A, const half8* B, int koff,
@@ -1046,18 +1048,24 @@ int x3_pack_population(const double* X, const double* w, int64_t N, int d,
 constexpr int64_t X3_NEST_CAP = 16384;
 inline int64_t x3_nest_rows(int64_t M) { return M < X3_NEST_CAP ? M : X3_NEST_CAP; }
 
-// the main launch's plan, then (hinted calls) room for the nested exact
-// pass over up to X3_NEST_CAP rescued candidates: their rows, results and
-// its own plan
-size_t x3_logpdf_workspace(int64_t M, int64_t N, int r) {
-  const size_t main = plan_x3_ws(make_plan_x3(M, N, r));
-  const int64_t m1 = x3_nest_rows(M > 0 ? M : 1);
-  size_t nested = 0;
-  size_only<double>(nested, (size_t)m1 * 64);           // rows (d <= 64)
-  size_only<double>(nested, (size_t)m1);                // results
-  size_only<char>(nested, plan_x3_ws(make_plan_x3(m1, N, r, true)));  // the nested plan
-  return main + nested + 256;
-}
+// the main launch's plan, then room for the nested exact pass of a hinted
+// call over up to X3_NEST_CAP rescued candidates: their rows, results and
+// its own workspace.  The nested pass (fine) is the plan alone.
+struct X3Ws {
+  PlanX3 p; X3PlanWs main; double* xs; double* outs; void* nested_ws; size_t nested_bytes;
+  void carve(Carver& cv, int64_t M, int64_t N, int r, bool fine) {
+    p = make_plan_x3(M, N, r, fine);
+    main.carve(cv, p);
+    if (fine) return;
+    const int64_t m1 = x3_nest_rows(M > 0 ? M : 1);
+    xs = cv.take<double>((size_t)m1 * 64);   // rows (d <= 64)
+    outs = cv.take<double>((size_t)m1);      // results
+    nested_bytes = measure<X3Ws>(m1, N, r, true);
+    nested_ws = cv.take<char>(nested_bytes);
+  }
+};
+
+size_t x3_logpdf_workspace(int64_t M, int64_t N, int r) { return measure<X3Ws>(M, N, r, false); }
 
 // fp64 rescue of the list entries [q_begin, *nres) (count on the device):
 // launch pairs over slot ranges of the main plan's partial arrays (free once
@@ -1087,19 +1095,10 @@ int x3_logpdf(const double* x, int64_t M, int d, const void* packed,
               hipStream_t s, int prof_channel, const unsigned int* count_dev) {
   if (r > MAX_R)
     return set_error(ABC_ERR_UNSUPPORTED, "mvn x3: rank %d > %d", r, MAX_R);
-  PlanX3 p = make_plan_x3(M, N, r, count_dev != nullptr);
-  if (ws_bytes < plan_x3_ws(p))
-    return set_error(ABC_ERR_WORKSPACE, "mvn x3: workspace %zu < %zu", ws_bytes,
-                     plan_x3_ws(p));
-  Carver cv(ws, ws_bytes);
-  _Float16* Bimg = cv.take<_Float16>((size_t)p.MTpad * p.KB * 64 * 8);
-  int32_t* cflags = cv.take<int32_t>((size_t)p.Mpad);
-  float* cand_o = cv.take<float>((size_t)p.Mpad);
-  double* po = cv.take<double>((size_t)p.nchunk * p.Mpad);
-  double* pl = cv.take<double>((size_t)p.nchunk * p.Mpad);
-  int64_t* rescue = cv.take<int64_t>((size_t)p.Mpad);
-  unsigned int* nres = cv.take<unsigned int>(64);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "mvn x3: workspace carve");
+  X3Ws k;
+  ABC_CARVE(k, "mvn x3", M, N, r, count_dev != nullptr);
+  const PlanX3& p = k.p;
+  auto [Bimg, cflags, cand_o, po, pl, rescue, nres] = k.main;
   const Header* hdr = (const Header*)packed;
   const half8* Aimg = (const half8*)((const char*)packed + HDR);
   ABC_HIP(hipMemsetAsync(nres, 0, sizeof(unsigned int), s));
@@ -1138,17 +1137,13 @@ int x3_logpdf(const double* x, int64_t M, int d, const void* packed,
     // one call, never seen on the configs) take the fp64 rescue, equally
     // within the parity bar but not bitwise the nested pass's values.
     const int64_t Mn = x3_nest_rows(M);
-    Carver sub(cv.rest(), cv.rest_bytes());
-    double* xs = sub.take<double>((size_t)Mn * d);
-    double* outs = sub.take<double>((size_t)Mn);
-    const size_t need = plan_x3_ws(make_plan_x3(Mn, N, r, true));
-    void* ws2 = sub.take<char>(need);
-    if (!sub.ok) return set_error(ABC_ERR_WORKSPACE, "mvn x3: nested rescue workspace");
+    double *xs = k.xs, *outs = k.outs;
     hipLaunchKernelGGL(x3_gather_rescued, dim3((unsigned)ceil_div(Mn * d, 256)),
                        dim3(256), 0, s, rescue, nres, Mn, x, d, xs);
     ABC_LAUNCHED();
     const int rc2 = x3_logpdf(xs, Mn, d, packed, X, w, N, mu, U, r, log_const, log_norm,
-                              outs, nullptr, ws2, need, s, ABC_PROF_RESCUE, nres);
+                              outs, nullptr, k.nested_ws, k.nested_bytes, s, ABC_PROF_RESCUE,
+                              nres);
     if (rc2) return rc2;
     hipLaunchKernelGGL(x3_scatter_rescued, dim3((unsigned)ceil_div(Mn, 256)), dim3(256), 0,
                        s, rescue, nres, Mn, outs, out);

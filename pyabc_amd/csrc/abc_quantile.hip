@@ -75,10 +75,12 @@ __device__ __forceinline__ double qval(u64 k) {
 // per-call control block, zero when a call starts (the workspace is zeroed
 // once; the gather's last block resets it): the global
 // key range (kmin stored complemented, so zero is the identity of the max
-// atomics), the last-block counters of the three multi-block stages (the
-// one-launch path: done[0] its arrival counter, done[1] its hand-off flag),
-// the fixed-point total and the list counter; pad != 0 marks a one-launch
-// call whose wait timed out
+// atomics), the last-block counters of the three multi-block stages of the
+// four-launch path, the fixed-point total and the list counter; pad != 0
+// marks a one-launch call whose wait timed out.  The one-launch path never
+// touches done[]: its arrival counters (8 group lines, one top line), its
+// hand-off flags and its range slots are the hs lines (WQ_HS_*) that follow
+// this block in the workspace; of ctl it shares only tot, list_n and pad
 struct WqCtl {
   u64 nkmin, kmax, wmax;
   unsigned int done[4];
@@ -1045,20 +1047,26 @@ int wq_blocks(int64_t N) {
 
 using namespace abc;
 
-extern "C" size_t abc_weighted_quantile_workspace(int64_t N) {
-  const int nb = wq_blocks(N > 0 ? N : 1);
-  size_t off = 0;
-  size_only<WqCtl>(off, 1);
-  size_only<unsigned int>(off, (size_t)WQ_HS_LINES * WQ_HS_STRIDE);
-  size_only<unsigned int>(off, (size_t)WQ_ONE_LEVELS * WQ_NB);
-  size_only<u64>(off, (size_t)WQ_ONE_LEVELS * WQ_NB);
-  size_only<WqDesc>(off, 2);
-  size_only<u64>(off, WQ_CAP);
-  size_only<int>(off, WQ_CAP);
-  size_only<double>(off, WQ_CAP);
-  size_only<double>(off, (size_t)2 * nb);
-  return off + 256;
-}
+// ctl stays first: the caller zero-fills the buffer once and the calls keep
+// ctl and hs zero between them
+struct QuantileWs {
+  WqCtl* ctl; unsigned int* hs; unsigned int* ghc; u64* ghw; WqDesc* desc;
+  u64* lkey; int* lidx; double* lw; double* psum;
+  void carve(Carver& cv, int64_t N) {
+    ctl = cv.take<WqCtl>(1);
+    hs = cv.take<unsigned int>((size_t)WQ_HS_LINES * WQ_HS_STRIDE);
+    // levels 1 | 2 (| 3: the one-launch path)
+    ghc = cv.take<unsigned int>((size_t)WQ_ONE_LEVELS * WQ_NB);
+    ghw = cv.take<u64>((size_t)WQ_ONE_LEVELS * WQ_NB);
+    desc = cv.take<WqDesc>(2);
+    lkey = cv.take<u64>(WQ_CAP);
+    lidx = cv.take<int>(WQ_CAP);
+    lw = cv.take<double>(WQ_CAP);
+    psum = cv.take<double>((size_t)2 * wq_blocks(N > 0 ? N : 1));
+  }
+};
+
+extern "C" size_t abc_weighted_quantile_workspace(int64_t N) { return measure<QuantileWs>(N); }
 
 // Launches: range, level-1 histogram (its
 // last block picks), level-2 histogram (exits at once when level 1 fits; its
@@ -1069,23 +1077,12 @@ extern "C" int abc_weighted_quantile(const double* points, const double* w, int6
                                      void* stream) {
   ABC_CHECK_ARG(N >= 1 && N < (1ll << 31), "quantile: bad N");
   ABC_CHECK_ARG(points && w && q && ws, "quantile: null pointer");
-  if (ws_bytes < abc_weighted_quantile_workspace(N))
-    return set_error(ABC_ERR_WORKSPACE, "quantile: workspace too small");
+  QuantileWs k;
+  ABC_CARVE(k, "quantile", N);
   hipStream_t s = as_stream(stream);
   const int nb = wq_blocks(N);
   const int64_t chunk = ceil_div(N, nb);
-  Carver cv(ws, ws_bytes);
-  WqCtl* ctl = cv.take<WqCtl>(1);
-  unsigned int* hs = cv.take<unsigned int>((size_t)WQ_HS_LINES * WQ_HS_STRIDE);
-  // levels 1 | 2 (| 3: the one-launch path)
-  unsigned int* ghc = cv.take<unsigned int>((size_t)WQ_ONE_LEVELS * WQ_NB);
-  u64* ghw = cv.take<u64>((size_t)WQ_ONE_LEVELS * WQ_NB);
-  WqDesc* desc = cv.take<WqDesc>(2);
-  u64* lkey = cv.take<u64>(WQ_CAP);
-  int* lidx = cv.take<int>(WQ_CAP);
-  double* lw = cv.take<double>(WQ_CAP);
-  double* psum = cv.take<double>((size_t)2 * nb);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "quantile: carve");
+  auto [ctl, hs, ghc, ghw, desc, lkey, lidx, lw, psum] = k;
   if (N <= WQ_ONE_MAX && nb <= resident_blocks(wq_onepass_kernel, WQ_T, 0)) {
     hipLaunchKernelGGL(wq_onepass_kernel, dim3(nb), dim3(WQ_T), 0, s, points, w, N, chunk,
                        alpha, ctl, hs, desc, ghc, ghw, lkey, lidx, lw, psum, q);

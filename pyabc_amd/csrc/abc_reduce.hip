@@ -463,14 +463,19 @@ __global__ void wscale_kernel(double* __restrict__ w, int64_t N,
 
 using namespace abc;
 
+struct MomentsWs {
+  double* p1; double* p2; double* pmax; double* tri;
+  void carve(Carver& cv, int64_t N, int d) {
+    const int64_t nb2 = d > 64 ? wide_blocks(N > 0 ? N : 1, d) : MOM_BLOCKS;
+    p1 = cv.take<double>((size_t)MOM_BLOCKS * (2 + d));
+    p2 = cv.take<double>((size_t)nb2 * d * d);
+    pmax = cv.take<double>((size_t)MOM_BLOCKS);
+    tri = cv.take<double>((size_t)d * d);
+  }
+};
+
 extern "C" size_t abc_weighted_moments_workspace(int64_t N, int d) {
-  const int64_t nb2 = d > 64 ? wide_blocks(N > 0 ? N : 1, d) : MOM_BLOCKS;
-  size_t off = 0;
-  size_only<double>(off, (size_t)MOM_BLOCKS * (2 + d));
-  size_only<double>(off, (size_t)nb2 * d * d);
-  size_only<double>(off, (size_t)MOM_BLOCKS);
-  size_only<double>(off, (size_t)d * d);
-  return off + 256;
+  return measure<MomentsWs>(N, d);
 }
 
 extern "C" int abc_weighted_moments(const double* X, const double* w,
@@ -478,13 +483,9 @@ extern "C" int abc_weighted_moments(const double* X, const double* w,
                                     size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(N >= 1 && d >= 1 && d <= ABC_MAX_D, "moments: bad N=%lld d=%d", (long long)N, d);
   ABC_CHECK_ARG(X && w && out && ws, "moments: null pointer");
-  if (ws_bytes < abc_weighted_moments_workspace(N, d))
-    return set_error(ABC_ERR_WORKSPACE, "moments: workspace too small");
-  Carver cv(ws, ws_bytes);
-  double* p1 = cv.take<double>((size_t)MOM_BLOCKS * (2 + d));
-  double* p2 = cv.take<double>((size_t)(d > 64 ? wide_blocks(N, d) : MOM_BLOCKS) * d * d);
-  double* pmax = cv.take<double>((size_t)MOM_BLOCKS);
-  double* tri = cv.take<double>((size_t)d * d);
+  MomentsWs k;
+  ABC_CARVE(k, "moments", N, d);
+  auto [p1, p2, pmax, tri] = k;
   hipStream_t s = as_stream(stream);
   switch (d) {
 #define ABC_MOM_CASE(D) \
@@ -527,19 +528,24 @@ extern "C" int abc_weighted_moments(const double* X, const double* w,
   return ABC_OK;
 }
 
-extern "C" size_t abc_scan_workspace(int64_t N) {
-  return align_up(sizeof(double) * (size_t)(ceil_div(N > 0 ? N : 1, SCAN_TILE)), 256) + 256;
-}
+struct ScanWs {
+  double* sums;   // per-tile totals, then their scan
+  void carve(Carver& cv, int64_t N) {
+    sums = cv.take<double>((size_t)ceil_div(N > 0 ? N : 1, SCAN_TILE));
+  }
+};
+
+extern "C" size_t abc_scan_workspace(int64_t N) { return measure<ScanWs>(N); }
 
 extern "C" int abc_inclusive_scan_f64(const double* in, double* out, int64_t N,
                                       void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(N >= 0, "scan: N < 0");
   if (N == 0) return ABC_OK;
   ABC_CHECK_ARG(in && out && ws, "scan: null pointer");
-  if (ws_bytes < abc_scan_workspace(N))
-    return set_error(ABC_ERR_WORKSPACE, "scan: workspace too small");
+  ScanWs k;
+  ABC_CARVE(k, "scan", N);
   const int64_t ntile = ceil_div(N, SCAN_TILE);
-  double* sums = static_cast<double*>(ws);
+  double* sums = k.sums;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)ntile), dim3(SCAN_T), 0, s, in, N, sums);
   ABC_LAUNCHED();
@@ -601,20 +607,25 @@ extern "C" int abc_importance_weights(const double* prior_logpdf,
   return ABC_OK;
 }
 
+struct NormalizeWs {
+  double* part;   // (sum w, sum w^2) per block
+  void carve(Carver& cv) { part = cv.take<double>(2 * NW_BLOCKS); }
+};
+
 extern "C" size_t abc_normalize_weights_workspace(int64_t N) {
   (void)N;
-  return sizeof(double) * 2 * NW_BLOCKS + 256;
+  return measure<NormalizeWs>();
 }
 
 extern "C" int abc_normalize_weights(double* w, int64_t N, double* stats,
                                      void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(N >= 1, "normalize: N < 1");
   ABC_CHECK_ARG(w && stats && ws, "normalize: null pointer");
-  if (ws_bytes < abc_normalize_weights_workspace(N))
-    return set_error(ABC_ERR_WORKSPACE, "normalize: workspace too small");
+  NormalizeWs k;
+  ABC_CARVE(k, "normalize");
   hipStream_t s = as_stream(stream);
   const int nblk = (int)(ceil_div(N, 256) < NW_BLOCKS ? ceil_div(N, 256) : NW_BLOCKS);
-  double* part = static_cast<double*>(ws);
+  double* part = k.part;
   hipLaunchKernelGGL(wsum_kernel, dim3(nblk), dim3(256), 0, s, w, N, part);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(wsum_final, dim3(1), dim3(64), 0, s, part, nblk, stats);

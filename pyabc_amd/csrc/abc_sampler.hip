@@ -428,17 +428,22 @@ extern "C" int abc_pnorm(const double* x, int64_t B, int S, const double* x0,
   return ABC_OK;
 }
 
-extern "C" size_t abc_compact_workspace(int64_t B) {
-  return align_up(sizeof(int64_t) * (size_t)ceil_div(B > 0 ? B : 1, CT_TILE), 256) + 256;
-}
+struct CompactWs {
+  int64_t* tiles;   // accepted per tile, then their exclusive scan
+  void carve(Carver& c, int64_t B) {
+    tiles = c.take<int64_t>((size_t)ceil_div(B > 0 ? B : 1, CT_TILE));
+  }
+};
+
+extern "C" size_t abc_compact_workspace(int64_t B) { return measure<CompactWs>(B); }
 
 extern "C" int abc_accept_compact(const double* d, int64_t B, double eps,
                                   int64_t* idx, int64_t* count, void* ws,
                                   size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(B >= 0, "compact: B < 0");
   ABC_CHECK_ARG(count && ws, "compact: null pointer");
-  if (ws_bytes < abc_compact_workspace(B))
-    return set_error(ABC_ERR_WORKSPACE, "compact: workspace too small");
+  CompactWs w;
+  ABC_CARVE(w, "compact", B);
   hipStream_t s = as_stream(stream);
   if (B == 0) {
     ABC_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
@@ -446,7 +451,7 @@ extern "C" int abc_accept_compact(const double* d, int64_t B, double eps,
   }
   ABC_CHECK_ARG(d && idx, "compact: null pointer");
   const int64_t nt = ceil_div(B, CT_TILE);
-  int64_t* tiles = static_cast<int64_t*>(ws);
+  int64_t* tiles = w.tiles;
   hipLaunchKernelGGL(accept_count_kernel, dim3((unsigned)nt), dim3(CT_T), 0, s, d, B, eps, tiles);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(CT_T), 0, s, tiles, nt, count);

@@ -33,18 +33,9 @@
 // and column stored to scratch, and the partials of the fixed grid added in
 // a fixed order by colred_final.  No floating-point atomics; the result does
 // not depend on which blocks run first.
-#include "abc_common.h"
+#include "abc_column_ws.h"
 
 namespace abc {
-size_t select_ws_bytes(int64_t R, int S);
-size_t select_cmad_ws_bytes(int64_t R, int S);
-int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
-                      size_t ws_bytes, hipStream_t s);
-int column_absdev_median_select(const double* X, int64_t R, int S, const double* centre,
-                                double* out, void* ws, size_t ws_bytes, hipStream_t s);
-int column_cmad_select(const double* X, int64_t R, int S, const double* x0, double* out,
-                       void* ws, size_t ws_bytes, hipStream_t s);
-
 namespace {
 
 constexpr int RD_T = 256;       // threads per block
@@ -168,14 +159,11 @@ __global__ __launch_bounds__(RD_T) void colred_final(
 struct RedBufs {
   double* part;  // [2][RD_BLOCKS][S]
   double* mean;  // [S]
+  void carve(Carver& cv, int S) {
+    part = cv.take<double>((size_t)2 * RD_BLOCKS * S);
+    mean = cv.take<double>((size_t)S);
+  }
 };
-
-size_t red_ws_bytes(int S) {
-  size_t off = 0;
-  size_only<double>(off, (size_t)2 * RD_BLOCKS * S);
-  size_only<double>(off, (size_t)S);
-  return off + 256;
-}
 
 struct RedGrid {
   int CB, RPI, ctiles, nblk;
@@ -213,12 +201,7 @@ int red_final(const double* part, int plane, int64_t R, int S, int fin, const do
 #define ABC_TRY(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
 int column_mean_family(int kind, const double* X, int64_t R, int S, const double* x0, double* out,
-                       void* ws, size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  RedBufs b;
-  b.part = cv.take<double>((size_t)2 * RD_BLOCKS * S);
-  b.mean = cv.take<double>((size_t)S);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace carve");
+                       const RedBufs& b, hipStream_t s) {
   const double* none = nullptr;
   switch (kind) {
     case ABC_SCALE_BIAS:
@@ -258,6 +241,20 @@ bool scale_kind_reads_x0(int kind) {
   return kind != ABC_SCALE_MAD && kind != ABC_SCALE_MEAN_AD && kind != ABC_SCALE_STD;
 }
 
+// abc_column_scale's layout: that of the kind's kernels
+struct ScaleWs {
+  ColumnStatsWs stats; SelectBufs sel; CmadBufs cmad; RedBufs red;
+  void carve(Carver& cv, int kind, int64_t R, int S) {
+    switch (kind) {
+      case ABC_SCALE_MAD:
+      case ABC_SCALE_STD: stats.carve(cv, R, S); break;
+      case ABC_SCALE_MAD_TO_OBS: sel.carve(cv, R, S); break;
+      case ABC_SCALE_CMAD: cmad.carve(cv, R, S); break;
+      default: red.carve(cv, S);
+    }
+  }
+};
+
 }  // namespace
 }  // namespace abc
 
@@ -265,17 +262,7 @@ using namespace abc;
 
 extern "C" size_t abc_column_scale_workspace(int kind, int64_t R, int S) {
   if (!scale_kind_known(kind) || R < 1 || S < 1) return 0;
-  switch (kind) {
-    case ABC_SCALE_MAD:
-    case ABC_SCALE_STD:
-      return abc_column_stats_workspace(R, S);
-    case ABC_SCALE_MAD_TO_OBS:
-      return select_ws_bytes(R, S);
-    case ABC_SCALE_CMAD:
-      return select_cmad_ws_bytes(R, S);
-    default:
-      return red_ws_bytes(S);
-  }
+  return measure<ScaleWs>(kind, R, S);
 }
 
 extern "C" int abc_column_scale(int kind, const double* X, int64_t R, int S, const double* x0,
@@ -284,19 +271,19 @@ extern "C" int abc_column_scale(int kind, const double* X, int64_t R, int S, con
   ABC_CHECK_ARG(R >= 1 && S >= 1, "column_scale: bad R/S");
   ABC_CHECK_ARG(X && out && ws, "column_scale: null pointer");
   ABC_CHECK_ARG(x0 || !scale_kind_reads_x0(kind), "column_scale: kind %d needs x0", kind);
-  if (ws_bytes < abc_column_scale_workspace(kind, R, S))
-    return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace too small");
+  ScaleWs w;
+  ABC_CARVE(w, "column_scale", kind, R, S);
   hipStream_t s = as_stream(stream);
   switch (kind) {
-    case ABC_SCALE_MAD:  // the same calls, the same bits
-      return column_mad_select(X, R, S, out, ws, ws_bytes, s);
+    case ABC_SCALE_MAD:  // the same calls as abc_column_mad / abc_column_std, the same bits
+      return column_mad_select(X, R, S, out, w.stats.sel, s);
     case ABC_SCALE_STD:
-      return abc_column_std(X, R, S, out, ws, ws_bytes, stream);
+      return column_std(X, R, S, out, w.stats.sd, s);
     case ABC_SCALE_MAD_TO_OBS:
-      return column_absdev_median_select(X, R, S, x0, out, ws, ws_bytes, s);
+      return column_absdev_median_select(X, R, S, x0, out, w.sel, s);
     case ABC_SCALE_CMAD:
-      return column_cmad_select(X, R, S, x0, out, ws, ws_bytes, s);
+      return column_cmad_select(X, R, S, x0, out, w.cmad, s);
     default:
-      return column_mean_family(kind, X, R, S, x0, out, ws, ws_bytes, s);
+      return column_mean_family(kind, X, R, S, x0, out, w.red, s);
   }
 }

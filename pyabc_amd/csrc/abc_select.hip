@@ -34,7 +34,7 @@
 // next non-empty bin it is the minimum of that bin, taken in the next pass
 // (LDS 64-bit atomic min).  Results are exact and bitwise deterministic (the
 // selection does not depend on the order of the compacted keys).
-#include "abc_common.h"
+#include "abc_column_ws.h"
 
 namespace abc {
 namespace {
@@ -363,30 +363,6 @@ __global__ __launch_bounds__(SEL_T) void col_select_kernel(
 
 }  // namespace
 
-size_t select_ws_bytes(int64_t R, int S) {
-  size_t off = 0;
-  size_only<uint64_t>(off, (size_t)R * S);             // window keys (worst case: all)
-  size_only<uint64_t>(off, (size_t)2 * S);             // windows [lo, hi]
-  size_only<unsigned long long>(off, (size_t)2 * S);   // in-window / below counts
-  size_only<double>(off, (size_t)S);                   // medians
-  return off + 256;
-}
-
-// the buffers of one select pass, carved from the caller's workspace
-struct SelectBufs {
-  uint64_t* scratch;
-  uint64_t* win;
-  unsigned long long* cnt;
-  double* med;
-};
-static bool carve_select(Carver& cv, int64_t R, int S, SelectBufs& b) {
-  b.scratch = cv.take<uint64_t>((size_t)R * S);
-  b.win = cv.take<uint64_t>((size_t)2 * S);
-  b.cnt = cv.take<unsigned long long>((size_t)2 * S);
-  b.med = cv.take<double>((size_t)S);
-  return cv.ok;
-}
-
 // One select pass (sample -> bracket -> select): DEV = false
 // dst[c] = median_c(X[:, c]); DEV = true dst[c] = median_c(|X[:, c] - centre[c]|)
 template <bool DEV>
@@ -416,24 +392,15 @@ static int select_pass(const double* X, int64_t R, int S, const double* centre, 
   return ABC_OK;
 }
 
-// out[c] = median_c(|X[:, c] - median_c(X[:, c])|)
-int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
-                      size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  SelectBufs b;
-  if (!carve_select(cv, R, S, b)) return set_error(ABC_ERR_WORKSPACE, "column_mad: workspace carve");
+int column_mad_select(const double* X, int64_t R, int S, double* out, const SelectBufs& b,
+                      hipStream_t s) {
   int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
   if (rc) return rc;
   return select_pass<true>(X, R, S, (const double*)b.med, out, b, s);
 }
 
-// out[c] = median_c(|X[:, c] - centre[c]|): one of the MAD's two passes
 int column_absdev_median_select(const double* X, int64_t R, int S, const double* centre,
-                                double* out, void* ws, size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  SelectBufs b;
-  if (!carve_select(cv, R, S, b))
-    return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace carve");
+                                double* out, const SelectBufs& b, hipStream_t s) {
   return select_pass<true>(X, R, S, centre, out, b, s);
 }
 
@@ -444,20 +411,10 @@ __global__ void add_columns_kernel(const double* __restrict__ a, int S, double* 
 }
 }  // namespace
 
-size_t select_cmad_ws_bytes(int64_t R, int S) {
-  size_t off = select_ws_bytes(R, S);
-  size_only<double>(off, (size_t)S);                   // the MAD beside the MAD to x0
-  return off + 256;
-}
-
-// out[c] = MAD_c + median_c(|X[:, c] - x0[c]|): three select passes, one add
 int column_cmad_select(const double* X, int64_t R, int S, const double* x0, double* out,
-                       void* ws, size_t ws_bytes, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
-  SelectBufs b;
-  carve_select(cv, R, S, b);
-  double* mad = cv.take<double>((size_t)S);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "column_scale: workspace carve");
+                       const CmadBufs& w, hipStream_t s) {
+  const SelectBufs& b = w.sel;
+  double* mad = w.mad;
   int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
   if (rc) return rc;
   rc = select_pass<true>(X, R, S, (const double*)b.med, mad, b, s);

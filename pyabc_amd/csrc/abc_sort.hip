@@ -16,7 +16,7 @@
 // histogram is laid out [segment][digit][tile], and one global exclusive scan
 // over it yields per-segment offsets because every segment holds exactly
 // seg_len items.
-#include "abc_common.h"
+#include "abc_column_ws.h"
 
 namespace abc {
 namespace {
@@ -226,38 +226,21 @@ __global__ __launch_bounds__(S1_T) void exscan_single(const int64_t* __restrict_
     if (k < per && b0 + k < n) { out[b0 + k] = run; run += v[k]; }
 }
 
+// a (key, value) sort of N pairs
 struct SortBufs {
   uint64_t* k0; uint64_t* k1; double* v0; double* v1;
   int64_t* hist; int64_t* off; int64_t* sums;
+  void carve(Carver& cv, int64_t N) {
+    const int64_t nh = RDIG * ceil_div(N > 0 ? N : 1, RTILE);
+    k0 = cv.take<uint64_t>((size_t)N);
+    k1 = cv.take<uint64_t>((size_t)N);
+    v0 = cv.take<double>((size_t)N);
+    v1 = cv.take<double>((size_t)N);
+    hist = cv.take<int64_t>((size_t)nh);
+    off = cv.take<int64_t>((size_t)nh);
+    sums = cv.take<int64_t>((size_t)ceil_div(nh, STILE) + 1);
+  }
 };
-
-size_t sort_ws_bytes(int64_t nseg, int64_t seg_len, bool vals) {
-  const int64_t tps = ceil_div(seg_len > 0 ? seg_len : 1, RTILE);
-  const int64_t nh = nseg * RDIG * tps;
-  const int64_t n = nseg * seg_len;
-  size_t off = 0;
-  size_only<uint64_t>(off, (size_t)n);
-  size_only<uint64_t>(off, (size_t)n);
-  if (vals) { size_only<double>(off, (size_t)n); size_only<double>(off, (size_t)n); }
-  size_only<int64_t>(off, (size_t)nh);
-  size_only<int64_t>(off, (size_t)nh);
-  size_only<int64_t>(off, (size_t)ceil_div(nh, STILE) + 1);
-  return off + 256;
-}
-
-bool carve_sort(Carver& cv, int64_t nseg, int64_t seg_len, bool vals, SortBufs& b) {
-  const int64_t tps = ceil_div(seg_len > 0 ? seg_len : 1, RTILE);
-  const int64_t nh = nseg * RDIG * tps;
-  const int64_t n = nseg * seg_len;
-  b.k0 = cv.take<uint64_t>((size_t)n);
-  b.k1 = cv.take<uint64_t>((size_t)n);
-  b.v0 = vals ? cv.take<double>((size_t)n) : nullptr;
-  b.v1 = vals ? cv.take<double>((size_t)n) : nullptr;
-  b.hist = cv.take<int64_t>((size_t)nh);
-  b.off = cv.take<int64_t>((size_t)nh);
-  b.sums = cv.take<int64_t>((size_t)ceil_div(nh, STILE) + 1);
-  return cv.ok;
-}
 
 // Sorts keys (already in b.k0, values in b.v0); result lands in b.k0/b.v0
 // (8 passes = even number of swaps).
@@ -336,7 +319,6 @@ __global__ void quantile_pick_kernel(const uint64_t* __restrict__ keys,
 }
 
 // ---- column std (np.std, two-pass) -------------------------------------------
-constexpr int CS_BLOCKS = 256;
 __global__ __launch_bounds__(256) void colsum_kernel(const double* __restrict__ X,
                                                      int64_t R, int S,
                                                      const double* __restrict__ mean,
@@ -379,19 +361,26 @@ __global__ void colsum_final(const double* __restrict__ part, int nblk, int S,
 }
 
 }  // namespace
-}  // namespace abc
 
-namespace abc {
-size_t select_ws_bytes(int64_t R, int S);
-int column_mad_select(const double* X, int64_t R, int S, double* out, void* ws,
-                      size_t ws_bytes, hipStream_t s);
+int column_std(const double* X, int64_t R, int S, double* out, const ColumnStdBufs& b,
+               hipStream_t s) {
+  const int nblk = (int)(R < CS_BLOCKS ? R : CS_BLOCKS);
+  hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)nullptr, b.part);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, b.part, nblk, S, R, b.mean, false);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)b.mean, b.part);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, b.part, nblk, S, R, out, true);
+  ABC_LAUNCHED();
+  return ABC_OK;
+}
+
 }  // namespace abc
 
 using namespace abc;
 
-extern "C" size_t abc_sort_pairs_workspace(int64_t N) {
-  return sort_ws_bytes(1, N, true);
-}
+extern "C" size_t abc_sort_pairs_workspace(int64_t N) { return measure<SortBufs>(N); }
 
 extern "C" int abc_sort_pairs_f64(const double* keys, const double* vals,
                                   int64_t N, double* keys_out,
@@ -400,12 +389,9 @@ extern "C" int abc_sort_pairs_f64(const double* keys, const double* vals,
   ABC_CHECK_ARG(N >= 0, "sort: N < 0");
   if (N == 0) return ABC_OK;
   ABC_CHECK_ARG(keys && vals && keys_out && vals_out && ws, "sort: null pointer");
-  if (ws_bytes < sort_ws_bytes(1, N, true))
-    return set_error(ABC_ERR_WORKSPACE, "sort: workspace too small");
-  hipStream_t s = as_stream(stream);
-  Carver cv(ws, ws_bytes);
   SortBufs b;
-  if (!carve_sort(cv, 1, N, true, b)) return set_error(ABC_ERR_WORKSPACE, "sort: carve");
+  ABC_CARVE(b, "sort", N);
+  hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(to_keys_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, keys, N, b.k0);
   ABC_LAUNCHED();
   ABC_HIP(hipMemcpyAsync(b.v0, vals, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
@@ -417,11 +403,19 @@ extern "C" int abc_sort_pairs_f64(const double* keys, const double* vals,
   return ABC_OK;
 }
 
+// sort | cumulated weights | the scan's own workspace
+struct SortedQuantileWs {
+  SortBufs sort; double* cs; void* scan_ws; size_t scan_bytes;
+  void carve(Carver& cv, int64_t N) {
+    sort.carve(cv, N);
+    cs = cv.take<double>((size_t)(N > 0 ? N : 1));
+    scan_bytes = abc_scan_workspace(N);
+    scan_ws = cv.take<char>(scan_bytes);
+  }
+};
+
 extern "C" size_t abc_weighted_quantile_sorted_workspace(int64_t N) {
-  size_t off = sort_ws_bytes(1, N, true);
-  size_only<double>(off, (size_t)(N > 0 ? N : 1));  // cumsum
-  off += abc_scan_workspace(N) + 256;
-  return off + 256;
+  return measure<SortedQuantileWs>(N);
 }
 
 extern "C" int abc_weighted_quantile_sorted(const double* points, const double* w,
@@ -429,65 +423,42 @@ extern "C" int abc_weighted_quantile_sorted(const double* points, const double* 
                                      void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(N >= 1, "quantile: N < 1");
   ABC_CHECK_ARG(points && w && q && ws, "quantile: null pointer");
-  if (ws_bytes < abc_weighted_quantile_sorted_workspace(N))
-    return set_error(ABC_ERR_WORKSPACE, "quantile: workspace too small");
+  SortedQuantileWs k;
+  ABC_CARVE(k, "quantile", N);
   hipStream_t s = as_stream(stream);
-  Carver cv(ws, ws_bytes);
-  SortBufs b;
-  if (!carve_sort(cv, 1, N, true, b)) return set_error(ABC_ERR_WORKSPACE, "quantile: carve");
-  double* cs = cv.take<double>((size_t)N);
-  size_t scan_bytes = abc_scan_workspace(N);
-  void* scan_ws = cv.take<char>(scan_bytes);
-  if (!cv.ok) return set_error(ABC_ERR_WORKSPACE, "quantile: carve");
+  SortBufs& b = k.sort;
   hipLaunchKernelGGL(to_keys_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, points, N, b.k0);
   ABC_LAUNCHED();
   ABC_HIP(hipMemcpyAsync(b.v0, w, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
   int rc = run_sort(b, 1, N, s);
   if (rc) return rc;
-  rc = abc_inclusive_scan_f64(b.v0, cs, N, scan_ws, scan_bytes, stream);
+  rc = abc_inclusive_scan_f64(b.v0, k.cs, N, k.scan_ws, k.scan_bytes, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(quantile_pick_kernel, dim3(1), dim3(64), 0, s, b.k0, b.v0, cs, N, alpha, q);
+  hipLaunchKernelGGL(quantile_pick_kernel, dim3(1), dim3(64), 0, s, b.k0, b.v0, k.cs, N, alpha, q);
   ABC_LAUNCHED();
   return ABC_OK;
 }
 
 extern "C" size_t abc_column_stats_workspace(int64_t R, int S) {
-  size_t a = select_ws_bytes(R, S);
-  size_t off = 0;
-  size_only<double>(off, (size_t)CS_BLOCKS * S);
-  size_only<double>(off, (size_t)S);
-  return (a > off ? a : off) + 256;
+  return measure<ColumnStatsWs>(R, S);
 }
 
 extern "C" int abc_column_std(const double* X, int64_t R, int S, double* out,
                               void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(R >= 1 && S >= 1, "column_std: bad R/S");
   ABC_CHECK_ARG(X && out && ws, "column_std: null pointer");
-  if (ws_bytes < abc_column_stats_workspace(R, S))
-    return set_error(ABC_ERR_WORKSPACE, "column_std: workspace too small");
-  hipStream_t s = as_stream(stream);
-  Carver cv(ws, ws_bytes);
-  double* part = cv.take<double>((size_t)CS_BLOCKS * S);
-  double* mean = cv.take<double>((size_t)S);
-  const int nblk = (int)(R < CS_BLOCKS ? R : CS_BLOCKS);
-  hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)nullptr, part);
-  ABC_LAUNCHED();
-  hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, part, nblk, S, R, mean, false);
-  ABC_LAUNCHED();
-  hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)mean, part);
-  ABC_LAUNCHED();
-  hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, part, nblk, S, R, out, true);
-  ABC_LAUNCHED();
-  return ABC_OK;
+  ColumnStatsWs k;
+  ABC_CARVE(k, "column_std", R, S);
+  return column_std(X, R, S, out, k.sd, as_stream(stream));
 }
 
 extern "C" int abc_column_mad(const double* X, int64_t R, int S, double* out,
                               void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(R >= 1 && S >= 1, "column_mad: bad R/S");
   ABC_CHECK_ARG(X && out && ws, "column_mad: null pointer");
-  if (ws_bytes < abc_column_stats_workspace(R, S))
-    return set_error(ABC_ERR_WORKSPACE, "column_mad: workspace too small");
+  ColumnStatsWs k;
+  ABC_CARVE(k, "column_mad", R, S);
   // exact radix select per column (abc_select.hip): median, then the median
   // of |x - median|; no full sort
-  return column_mad_select(X, R, S, out, ws, ws_bytes, as_stream(stream));
+  return column_mad_select(X, R, S, out, k.sel, as_stream(stream));
 }

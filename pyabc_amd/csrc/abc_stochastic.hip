@@ -247,9 +247,12 @@ extern "C" int abc_stochastic_accept(const double* dens, int64_t B,
   return ABC_OK;
 }
 
-extern "C" size_t abc_temper_workspace(void) {
-  return sizeof(double) * 2 * TS_BLOCKS + 256;
-}
+struct TemperWs {
+  double* part;   // two partial sums per block
+  void carve(Carver& c) { part = c.take<double>(2 * TS_BLOCKS); }
+};
+
+extern "C" size_t abc_temper_workspace(void) { return measure<TemperWs>(); }
 
 extern "C" int abc_temper_sums(const double* dens, const double* lr,
                                const double* lr_sub, int64_t R, double pdf_norm, int scale_log, int mode,
@@ -257,10 +260,10 @@ extern "C" int abc_temper_sums(const double* dens, const double* lr,
                                void* ws, size_t ws_bytes, void* stream) {
   ABC_CHECK_ARG(R >= 0 && mode >= 0 && mode <= 3, "temper_sums: bad R/mode");
   ABC_CHECK_ARG(out && ws && lr && (mode == 2 || dens), "temper_sums: null pointer");
-  if (ws_bytes < abc_temper_workspace())
-    return set_error(ABC_ERR_WORKSPACE, "temper_sums: workspace too small");
+  TemperWs w;
+  ABC_CARVE(w, "temper_sums");
   const int nb = (int)std::min<int64_t>(TS_BLOCKS, std::max<int64_t>(1, ceil_div(R, TS_T)));
-  double* part = static_cast<double*>(ws);
+  double* part = w.part;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(temper_partial_kernel, dim3(nb), dim3(TS_T), 0, s, dens, lr, lr_sub,
                      R, pdf_norm, scale_log, mode, beta, shift, part);
