@@ -452,6 +452,23 @@ __device__ __forceinline__ int64_t anc_bin(double x, double inv_step, int64_t G)
 // (X == nullptr: draw from the prior).  Separate instantiations keep the
 // prior draw's calls out of the transition kernels' register allocation.
 constexpr int PROP_MVN = 0, PROP_LOCAL = 1, PROP_PRIOR = 2;
+using PropModes = std::integer_sequence<int, PROP_MVN, PROP_LOCAL, PROP_PRIOR>;
+inline int proposal_mode(const double* X, bool per_particle_L) {
+  return X == nullptr ? PROP_PRIOR : (per_particle_L ? PROP_LOCAL : PROP_MVN);
+}
+
+// The dimensions every candidate kernel (propose_kernel, the fused round, its
+// regeneration and proposal kernels) is instantiated for with theta in D
+// registers; any other d <= 64 runs the runtime-d instantiation D = 0.
+using CandDims = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 10, 12, 16>;
+
+// f(D, MODE) as std::integral_constant values, for the candidate kernels'
+// <D, MODE> of dimension d and proposal mode `mode` (host code)
+template <class F>
+void dispatch_candidate(int d, int mode, F&& f) {
+  auto with_d = [&](auto D) { dispatch_int(PropModes{}, mode, [&](auto MODE) { f(D, MODE); }); };
+  if (!dispatch_int(CandDims{}, d, with_d)) with_d(std::integral_constant<int, 0>{});
+}
 
 // ---- LinearGaussianModel + PNormDistance -----------------------------------
 struct SimDistArgs {
@@ -645,7 +662,7 @@ __device__ __forceinline__ bool lazy_filter_ok(const BlockConsts& C, const Propo
 }
 
 // (contraction is off for the whole header, line 20; restated in each of
-// these three so that no include order or later edit can let the compiler
+// the p-norm functions so that no include order or later edit can let the compiler
 // turn s + v * v into an fma in one kernel and not in another: the round's
 // accept bit and the regenerated / staged distance must be the same bits)
 __device__ __forceinline__ double pterm(double v, double p) {
@@ -669,6 +686,58 @@ __device__ __forceinline__ double pnorm_finish(double s, double p) {
   if constexpr (PK == 2) return sqrt(s);
   return isinf(p) ? s : ((p == 1.0) ? s : (p == 2.0 ? sqrt(s) : pow(s, 1.0 / p)));
 }
+// PNormDistance of stored rows: the two summation orders abc_pnorm and the
+// accept tail abc_pnorm_accept share (one definition, so the tail's decision
+// is dist <= eps of abc_pnorm's bits); both finish through pnorm_finish<0>
+// (in pnorm_row once per branch, where the compiler folds its test of p).
+// Narrow rows: the distance of one row xr[0 .. S), summed in k order (xr in
+// global memory or LDS).
+__device__ __forceinline__ double pnorm_row(const double* xr, int S, const double* x0,
+                                            const double* wf, double p) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  if (isinf(p)) {
+    for (int k = 0; k < S; ++k) s = fmax(s, fabs(wf[k] * (xr[k] - x0[k])));
+    return pnorm_finish<0>(s, p);
+  }
+  for (int k = 0; k < S; ++k) s += pterm(fabs(wf[k] * (xr[k] - x0[k])), p);
+  return pnorm_finish<0>(s, p);
+}
+// Wide rows: one wave takes rows b0 .. b0 + PNORM_ROWS - 1 of x [B x S] at
+// once, so that many row loads are in flight per lane (one row per wave left
+// the HBM stream latency-bound at ~40% of peak).  Lanes stride over k
+// (coalesced); per row the order is lane-strided partials, then the wave
+// tree.  Rows past B read x0 (a zero term) and are not emitted; lane 0 calls
+// emit(r, distance of row b0 + r).  Every lane of the wave calls it.
+constexpr int PNORM_ROWS = 8;
+template <class F>
+__device__ __forceinline__ void pnorm_wave_rows(const double* x, int64_t b0, int64_t B, int S,
+                                                const double* x0, const double* wf, double p,
+                                                F&& emit) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const bool inf = isinf(p);
+  double s[PNORM_ROWS];
+#pragma unroll
+  for (int r = 0; r < PNORM_ROWS; ++r) s[r] = 0.0;
+  for (int k = lane; k < S; k += 64) {
+    const double wk = wf[k], ck = x0[k];
+    double v[PNORM_ROWS];
+#pragma unroll
+    for (int r = 0; r < PNORM_ROWS; ++r) v[r] = b0 + r < B ? x[(b0 + r) * S + k] : ck;
+#pragma unroll
+    for (int r = 0; r < PNORM_ROWS; ++r) {
+      const double a = fabs(wk * (v[r] - ck));
+      s[r] = inf ? fmax(s[r], a) : s[r] + pterm(a, p);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < PNORM_ROWS; ++r) {
+    const double t = inf ? wave_max(s[r]) : wave_sum(s[r]);
+    if (lane == 0 && b0 + r < B) emit(r, pnorm_finish<0>(t, p));
+  }
+}
+
 // one simulated statistic (simulate_lg_kernel's formula)
 __device__ __forceinline__ double lg_stat(double a, double sigma, double th_src, double e) {
   return a * th_src + sigma * e;
@@ -736,6 +805,21 @@ __device__ __forceinline__ double sim_pnorm_regs(const SimDistArgs& M, const Blo
     }
   }
   return s;
+}
+
+// The two above behind one call for the kernels templated on D: theta th in
+// D registers (D > 0) or a row of d values in memory (D == 0).
+template <int D, int PK = 0>
+__device__ __forceinline__ double sim_pnorm(const SimDistArgs& M, const BlockConsts& C,
+                                            const double* th, uint64_t g, uint32_t gen,
+                                            uint64_t seed, int q0, int q1, double s, double* x,
+                                            int xoff = 0) {
+  if constexpr (D > 0) {
+    return sim_pnorm_regs<D, PK>(M, C, *reinterpret_cast<const double(*)[D]>(th), g, gen, seed,
+                                 q0, q1, s, x, xoff);
+  } else {
+    return sim_pnorm_range<PK>(M, C, th, 1, g, gen, seed, q0, q1, s, x, xoff);
+  }
 }
 
 // The lazy early reject for CG candidates at once: theta_0..LAZY_KT-1 of

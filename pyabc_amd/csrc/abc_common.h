@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <math.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/abcgpu.h"
 
 namespace abc {
@@ -32,6 +34,18 @@ void profile_stop(hipStream_t s, int channel = ABC_PROF_DENSITY);
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// A runtime integer onto a compile-time one from a named list (host code):
+// f(std::integral_constant<int, D>{}) for the D of the list equal to d.
+// False when d is not in the list; the caller then takes its own fallback.
+// (A left fold: f's instantiations, and so the kernels they launch, are
+// emitted in list order; a right fold expands from the last entry.)
+// Every kernel templated on a dimension is chosen through this; the lists
+// are named next to the kernels they govern.
+template <int... Ds, class F>
+bool dispatch_int(std::integer_sequence<int, Ds...>, int d, F&& f) {
+  return (... || (d == Ds ? (f(std::integral_constant<int, Ds>{}), true) : false));
+}
 
 // Resident blocks of a kernel on the current device: the occupancy query x
 // CUs, cached per kernel and device (grids of ticket-scheduled kernels).
@@ -225,6 +239,28 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ---- block helpers -----------------------------------------------------------
+// Exclusive scan of one value per thread over a block of NT threads:
+// Hillis-Steele in LDS (sh[NT]), fixed order, so deterministic for doubles
+// too.  total receives the block's sum.  Every thread of the block calls it
+// (barriers inside); sh may be reused once it returns.
+template <class T, int NT>
+__device__ __forceinline__ T block_exscan(T v, T* sh, T& total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 1; o < NT; o <<= 1) {
+    const T add = (t >= o) ? sh[t - o] : T(0);
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  total = sh[NT - 1];
+  const T incl = sh[t];
+  __syncthreads();
+  return incl - v;
 }
 
 }  // namespace abc

@@ -48,13 +48,7 @@ __device__ __forceinline__ double evaluate_full(const RoundArgs& A, const BlockC
                                                 uint64_t g,
                                                 double* th, int64_t& j, int& att, double* x) {
   att = propose_one<D, MODE, true>(A.P, C, g, th, j);
-  double s;
-  if constexpr (D > 0) {
-    s = sim_pnorm_regs<D, PK>(A.M, C, *reinterpret_cast<const double(*)[D]>(th), g, A.P.gen,
-                          A.P.seed, 0, A.M.S, 0.0, x);
-  } else {
-    s = sim_pnorm_range<PK>(A.M, C, th, 1, g, A.P.gen, A.P.seed, 0, A.M.S, 0.0, x);
-  }
+  const double s = sim_pnorm<D, PK>(A.M, C, th, g, A.P.gen, A.P.seed, 0, A.M.S, 0.0, x);
   const double dist = pnorm_finish<PK>(s, A.M.p);
   return att <= A.P.max_attempts ? dist : NAN;
 }
@@ -82,14 +76,7 @@ __device__ __forceinline__ double evaluate_staged(const RoundArgs& A, const Bloc
   double s = 0.0;
   for (int k0 = 0; k0 < S; k0 += XCH) {
     const int k1 = k0 + XCH < S ? k0 + XCH : S;
-    if (valid) {
-      if constexpr (D > 0) {
-        s = sim_pnorm_regs<D, PK>(A.M, C, *reinterpret_cast<const double(*)[D]>(th), g,
-                                  A.P.gen, A.P.seed, k0, k1, s, stage[t], k0);
-      } else {
-        s = sim_pnorm_range<PK>(A.M, C, th, 1, g, A.P.gen, A.P.seed, k0, k1, s, stage[t], k0);
-      }
-    }
+    if (valid) s = sim_pnorm<D, PK>(A.M, C, th, g, A.P.gen, A.P.seed, k0, k1, s, stage[t], k0);
     __syncthreads();
     const int w = k1 - k0;
     for (int e = t; e < FR_T * w; e += FR_T) {
@@ -100,6 +87,19 @@ __device__ __forceinline__ double evaluate_staged(const RoundArgs& A, const Bloc
   }
   const double dist = pnorm_finish<PK>(s, A.M.p);
   return att <= A.P.max_attempts ? dist : NAN;
+}
+
+// A tile's accept bits tbits (32-bit LDS words, candidate tile0 + loc at bit
+// loc) leave as its first nwords 64-bit accept words, written by wave 0.
+// Every thread calls it, after the barrier that completes tbits.
+__device__ __forceinline__ void flush_accept_words(const uint32_t* tbits, int nwords,
+                                                   int64_t tile0, int64_t B, uint64_t* bits) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0 && lane < nwords) {
+    const uint64_t w = (uint64_t)tbits[2 * lane] | ((uint64_t)tbits[2 * lane + 1] << 32);
+    const int64_t word = tile0 / 64 + lane;
+    if (word * 64 < B) bits[word] = w;
+  }
 }
 
 // One tile of the round: candidates tile0 + [0, cpt * FR_T) (cpt per thread,
@@ -116,7 +116,7 @@ __device__ __forceinline__ void tile_body(const RoundArgs& A, const BlockConsts&
                                           uint64_t* __restrict__ bits,
                                           double* __restrict__ rec_x, TileLds T) {
   constexpr int DM = D > 0 ? D : 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int tn = cpt * FR_T;                  // candidates of the tile
   if (tid < tn / 32) T.tbits[tid] = 0u;
   if (tid == 0) T.qn = 0;
@@ -158,13 +158,7 @@ __device__ __forceinline__ void tile_body(const RoundArgs& A, const BlockConsts&
       if (b < B) {
         const uint64_t g = (uint64_t)(idx0 + b);
         att = propose_one<D, MODE, true>(A.P, C, g, th, j);
-        double s;
-        if constexpr (D > 0) {
-          s = sim_pnorm_regs<D, PK>(A.M, C, *reinterpret_cast<const double(*)[D]>(th), g,
-                                A.P.gen, A.P.seed, 0, 4, 0.0, nullptr);
-        } else {
-          s = sim_pnorm_range<PK>(A.M, C, th, 1, g, A.P.gen, A.P.seed, 0, 4, 0.0, nullptr);
-        }
+        const double s = sim_pnorm<D, PK>(A.M, C, th, g, A.P.gen, A.P.seed, 0, 4, 0.0, nullptr);
         if (att <= A.P.max_attempts && !(pnorm_finish<PK>(s, A.M.p) > eps)) {
           const int pos = atomicAdd(&T.qn, 1);
           T.queue[pos] = (uint16_t)loc;
@@ -188,12 +182,7 @@ __device__ __forceinline__ void tile_body(const RoundArgs& A, const BlockConsts&
     }
   }
   __syncthreads();
-  // accept words of the tile (wave 0)
-  if (wave == 0 && lane < tn / 64) {
-    const uint64_t w = (uint64_t)T.tbits[2 * lane] | ((uint64_t)T.tbits[2 * lane + 1] << 32);
-    const int64_t word = tile0 / 64 + lane;
-    if (word * 64 < B) bits[word] = w;
-  }
+  flush_accept_words(T.tbits, tn / 64, tile0, B, bits);
 }
 
 // ---- the round: tiles handed out by a ticket counter -------------------------
@@ -282,6 +271,8 @@ __device__ __forceinline__ void round_plain_body(RoundArgs A, int64_t idx0, int6
   for (;;) {
     if (it == cpt) {                      // block-uniform: the tile is done
       __syncthreads();
+      // flush_accept_words, inline: through the call the p = 2 round at d = 10
+      // spills (8 B of scratch at its 80 VGPRs)
       if (started && wave == 0 && lane < cpt * (FR_T / 64)) {
         const uint64_t w = (uint64_t)tbits[2 * lane] | ((uint64_t)tbits[2 * lane + 1] << 32);
         const int64_t word = tile0 / 64 + lane;
@@ -559,14 +550,12 @@ __global__ __launch_bounds__(256) void fused_propose_kernel(
 // and the UniformAcceptor test d <= eps (acceptor.py:235-244) and leaves only
 // the accept bits + per-tile counts of the fused round, whose scan and
 // bits_write turn them into the positions of the first `cap` accepted: no
-// distance array is written and re-read.  The arithmetic per row is
-// pnorm_row_kernel's (S <= 32: thread per row, k order) or pnorm_wave_kernel's
-// (wide rows: lane-strided partials then the wave tree), so the decision is
-// the one dist <= eps of abc_pnorm's value would give, and the kept rows'
-// distances recomputed by abc_pnorm are those bits.  A proposal that gave up
-// on the prior support (attempts > max_attempts) is never accepted, as
-// abc_mask_gave_up's NaN.
-constexpr int PA_ROWS = 8;    // rows in flight per wave (wide path)
+// distance array is written and re-read.  Each row's distance comes from the
+// functions abc_pnorm's kernels call (abc_candidate.h: pnorm_row for
+// S <= 32, pnorm_wave_rows for wide rows, pnorm_finish<0>), so the decision is
+// dist <= eps of abc_pnorm's value and the kept rows' distances recomputed by
+// abc_pnorm are those bits.  A proposal that gave up on the prior support
+// (attempts > max_attempts) is never accepted, as abc_mask_gave_up's NaN.
 // rows per LDS chunk of the row path: 256, fewer when 256 padded rows of S
 // doubles would pass 64 KB (S = 32: 248); even, so chunks stay 16-B aligned
 __host__ __device__ constexpr int pa_chunk_rows(int S) {
@@ -578,21 +567,17 @@ __global__ __launch_bounds__(FR_T) void pnorm_accept_kernel(
     const double* __restrict__ wf, double p, double eps, const int32_t* __restrict__ att,
     int max_attempts, uint64_t* __restrict__ bits) {
   __shared__ uint32_t tbits[FR_TILE / 32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t tile0 = (int64_t)blockIdx.x * FR_TILE;
   if (tid < FR_TILE / 32) tbits[tid] = 0u;
   __syncthreads();
-  const bool inf = isinf(p);
-  auto finish = [&](double t) {
-    return inf ? t : ((p == 1.0) ? t : (p == 2.0 ? sqrt(t) : pow(t, 1.0 / p)));
-  };
   auto ok = [&](int64_t b) { return att == nullptr || att[b] <= max_attempts; };
   if (!WIDE) {
     // chunks of RC rows (pa_chunk_rows: 256, or what 64 KB of LDS holds):
     // the chunk's RC * S contiguous doubles come in with 16-B coalesced loads
     // (the next chunk's held in registers while this one is summed), land in
     // LDS rows of stride S + 1 (2-way banked reads), and each thread sums its
-    // row in k order as abc_pnorm does
+    // row in k order (pnorm_row)
     extern __shared__ double pa_rows[];
     const int S1 = S + 1;
     const int RC = pa_chunk_rows(S);
@@ -640,51 +625,24 @@ __global__ __launch_bounds__(FR_T) void pnorm_accept_kernel(
       const int loc = it * RC + tid;
       const int64_t b = tile0 + loc;
       if (tid < RC && loc < FR_TILE && b < B) {
-        const double* xr = pa_rows + tid * S1;
-        double s = 0.0;
-        if (inf) {
-          for (int k = 0; k < S; ++k) s = fmax(s, fabs(wf[k] * (xr[k] - x0[k])));
-        } else {
-          for (int k = 0; k < S; ++k) s += pterm(fabs(wf[k] * (xr[k] - x0[k])), p);
-        }
-        if (finish(s) <= eps && ok(b)) atomicOr(&tbits[loc >> 5], 1u << (loc & 31));
+        const double dist = pnorm_row(pa_rows + tid * S1, S, x0, wf, p);
+        if (dist <= eps && ok(b)) atomicOr(&tbits[loc >> 5], 1u << (loc & 31));
       }
     }
   } else {
-    // wave w takes rows w * PA_ROWS + 4 PA_ROWS i of the tile
+    // wave w takes rows w * PNORM_ROWS + 4 PNORM_ROWS i of the tile
 #pragma unroll 1
-    for (int r0 = wave * PA_ROWS; r0 < FR_TILE; r0 += 4 * PA_ROWS) {
+    for (int r0 = (tid >> 6) * PNORM_ROWS; r0 < FR_TILE; r0 += 4 * PNORM_ROWS) {
       const int64_t b0 = tile0 + r0;
       if (b0 >= B) break;  // wave-uniform
-      double sr[PA_ROWS];
-#pragma unroll
-      for (int r = 0; r < PA_ROWS; ++r) sr[r] = 0.0;
-      for (int k = lane; k < S; k += 64) {
-        const double wk = wf[k], ck = x0[k];
-        double v[PA_ROWS];
-#pragma unroll
-        for (int r = 0; r < PA_ROWS; ++r) v[r] = b0 + r < B ? x[(b0 + r) * S + k] : ck;
-#pragma unroll
-        for (int r = 0; r < PA_ROWS; ++r) {
-          const double a = fabs(wk * (v[r] - ck));
-          sr[r] = inf ? fmax(sr[r], a) : sr[r] + pterm(a, p);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < PA_ROWS; ++r) {
-        const double t = inf ? wave_max(sr[r]) : wave_sum(sr[r]);
+      pnorm_wave_rows(x, b0, B, S, x0, wf, p, [&](int r, double dist) {
         const int loc = r0 + r;
-        if (lane == 0 && b0 + r < B && finish(t) <= eps && ok(b0 + r))
-          atomicOr(&tbits[loc >> 5], 1u << (loc & 31));
-      }
+        if (dist <= eps && ok(b0 + r)) atomicOr(&tbits[loc >> 5], 1u << (loc & 31));
+      });
     }
   }
   __syncthreads();
-  if (wave == 0 && lane < FR_WORDS) {
-    const uint64_t w = (uint64_t)tbits[2 * lane] | ((uint64_t)tbits[2 * lane + 1] << 32);
-    const int64_t word = tile0 / 64 + lane;
-    if (word * 64 < B) bits[word] = w;
-  }
+  flush_accept_words(tbits, FR_WORDS, tile0, B, bits);
 }
 
 // *count and the positions of the first cap accepted from the range totals
@@ -810,66 +768,11 @@ int check_spec(const abc_candidate_spec* s) {
   return ABC_OK;
 }
 
-#define ABC_FUSED_DISPATCH(KERNEL, GRID, STREAM, ...)                          \
-  do {                                                                         \
-    const int mode_ = spec->X == nullptr ? PROP_PRIOR                          \
-                      : (spec->per_particle_L ? PROP_LOCAL : PROP_MVN);        \
-    switch (spec->d) {                                                         \
-      ABC_FUSED_CASE(KERNEL, 1, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 2, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 3, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 4, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 5, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 6, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 8, GRID, STREAM, __VA_ARGS__)                     \
-      ABC_FUSED_CASE(KERNEL, 10, GRID, STREAM, __VA_ARGS__)                    \
-      ABC_FUSED_CASE(KERNEL, 12, GRID, STREAM, __VA_ARGS__)                    \
-      ABC_FUSED_CASE(KERNEL, 16, GRID, STREAM, __VA_ARGS__)                    \
-      default:                                                                 \
-        ABC_FUSED_CASE_BODY(KERNEL, 0, GRID, STREAM, __VA_ARGS__)              \
-    }                                                                          \
-  } while (0)
-#define ABC_FUSED_CASE_BODY(KERNEL, DD, GRID, STREAM, ...)                     \
-  if (mode_ == PROP_MVN)                                                       \
-    hipLaunchKernelGGL((KERNEL<DD, PROP_MVN>), GRID, dim3(256), 0, STREAM,     \
-                       __VA_ARGS__);                                           \
-  else if (mode_ == PROP_LOCAL)                                                \
-    hipLaunchKernelGGL((KERNEL<DD, PROP_LOCAL>), GRID, dim3(256), 0, STREAM,   \
-                       __VA_ARGS__);                                           \
-  else                                                                         \
-    hipLaunchKernelGGL((KERNEL<DD, PROP_PRIOR>), GRID, dim3(256), 0, STREAM,   \
-                       __VA_ARGS__);                                           \
-  break;
-#define ABC_FUSED_CASE(KERNEL, DD, GRID, STREAM, ...)                          \
-  case DD: { ABC_FUSED_CASE_BODY(KERNEL, DD, GRID, STREAM, __VA_ARGS__) }
-
-// the same dispatch for a host launcher template FN<D, MODE>(args...)
-#define ABC_FUSED_CALL(FN, ...)                                                \
-  do {                                                                         \
-    const int mode_ = spec->X == nullptr ? PROP_PRIOR                          \
-                      : (spec->per_particle_L ? PROP_LOCAL : PROP_MVN);        \
-    switch (spec->d) {                                                         \
-      ABC_FUSED_CALL_CASE(FN, 1, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 2, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 3, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 4, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 5, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 6, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 8, __VA_ARGS__)                                  \
-      ABC_FUSED_CALL_CASE(FN, 10, __VA_ARGS__)                                 \
-      ABC_FUSED_CALL_CASE(FN, 12, __VA_ARGS__)                                 \
-      ABC_FUSED_CALL_CASE(FN, 16, __VA_ARGS__)                                 \
-      default:                                                                 \
-        ABC_FUSED_CALL_BODY(FN, 0, __VA_ARGS__)                                \
-    }                                                                          \
-  } while (0)
-#define ABC_FUSED_CALL_BODY(FN, DD, ...)                                       \
-  if (mode_ == PROP_MVN) FN<DD, PROP_MVN>(__VA_ARGS__);                        \
-  else if (mode_ == PROP_LOCAL) FN<DD, PROP_LOCAL>(__VA_ARGS__);               \
-  else FN<DD, PROP_PRIOR>(__VA_ARGS__);                                        \
-  break;
-#define ABC_FUSED_CALL_CASE(FN, DD, ...)                                       \
-  case DD: { ABC_FUSED_CALL_BODY(FN, DD, __VA_ARGS__) }
+// the candidate kernels' <D, MODE> for a (checked) spec
+template <class F>
+void dispatch_spec(const abc_candidate_spec* spec, F&& f) {
+  dispatch_candidate(spec->d, proposal_mode(spec->X, spec->per_particle_L != 0), f);
+}
 
 }  // namespace
 }  // namespace abc
@@ -956,7 +859,9 @@ extern "C" int abc_candidates_round(const abc_candidate_spec* spec, int64_t idx0
   A.eps_dev = eps_dev;
   A.eps_scale = eps_scale;
   profile_start(s, ABC_PROF_CANDIDATES);
-  ABC_FUSED_CALL(launch_round, filt != 0, p == 2.0, A, idx0, B, eps, w.bits, w.ticket, rec_x, s);
+  dispatch_spec(spec, [&](auto D, auto MODE) {
+    launch_round<D(), MODE()>(filt != 0, p == 2.0, A, idx0, B, eps, w.bits, w.ticket, rec_x, s);
+  });
   profile_stop(s, ABC_PROF_CANDIDATES);
   ABC_LAUNCHED();
   return compact_accept_bits(w.bits, w.rtot, B, cap, idx, count, s);
@@ -1043,8 +948,10 @@ extern "C" int abc_candidates_propose(const abc_candidate_spec* spec, int64_t id
   const RoundArgs A = round_args(spec, box);
   const int64_t nb = ceil_div(B, (int64_t)FR_T * FP_CPT);
   ABC_CHECK_ARG(nb < (1ll << 31), "candidates_propose: too many blocks");
-  ABC_FUSED_DISPATCH(fused_propose_kernel, dim3((unsigned)nb), s, A, idx0, B, theta,
-                     prior_logpdf, ancestor, attempts);
+  dispatch_spec(spec, [&](auto D, auto MODE) {
+    hipLaunchKernelGGL((fused_propose_kernel<D(), MODE()>), dim3((unsigned)nb), dim3(256), 0, s,
+                       A, idx0, B, theta, prior_logpdf, ancestor, attempts);
+  });
   ABC_LAUNCHED();
   return ABC_OK;
 }
@@ -1061,8 +968,11 @@ extern "C" int abc_candidates_regen(const abc_candidate_spec* spec, int64_t idx0
   const RoundArgs A = round_args(spec, nullptr);  // box: per block, in LDS
   hipStream_t s = as_stream(stream);
   profile_start(s, ABC_PROF_REGEN);
-  ABC_FUSED_DISPATCH(fused_regen_kernel, dim3((unsigned)ceil_div(n, 256)), s, A, idx0, idx, n,
-                     n_dev, theta, prior_logpdf, ancestor, x, dist);
+  dispatch_spec(spec, [&](auto D, auto MODE) {
+    hipLaunchKernelGGL((fused_regen_kernel<D(), MODE()>), dim3((unsigned)ceil_div(n, 256)),
+                       dim3(256), 0, s, A, idx0, idx, n, n_dev, theta, prior_logpdf, ancestor, x,
+                       dist);
+  });
   profile_stop(s, ABC_PROF_REGEN);
   ABC_LAUNCHED();
   return ABC_OK;

@@ -1602,6 +1602,9 @@ int launch_pdf(const double* x, int64_t M, const double* X, const double* w,
 
 }  // namespace
 
+// the dimensions the fit and density kernels above are instantiated for
+using LocalDims = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+
 // d > 16: runtime-d kernels (abc_local_wide.hip)
 size_t local_wide_fit_workspace(int64_t N, int d);
 int local_wide_fit(const double* X, const double* w, int64_t N, int d, int64_t nq,
@@ -1616,13 +1619,9 @@ using namespace abc;
 
 extern "C" size_t abc_local_fit_workspace(int64_t N, int d) {
   if (d > 16) return local_wide_fit_workspace(N, d);
-  switch (d) {
-#define ABC_D(n) case n: return measure<FitWs<n>>(N);
-    ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
-    ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
-#undef ABC_D
-  }
-  return Carver::SLACK;
+  size_t bytes = Carver::SLACK;
+  dispatch_int(LocalDims{}, d, [&](auto D) { bytes = measure<FitWs<D()>>(N); });
+  return bytes;
 }
 
 extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
@@ -1639,23 +1638,19 @@ extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
   if (d > 16)
     return local_wide_fit(X, w, N, d, nq, scaling, eps, covs, inv_covs, dets, chol, log_norm,
                           ws, ws_bytes, s);
-  switch (d) {
-#define ABC_D(n) case n: return launch_fit<n>(X, w, N, nq, scaling, eps, covs, inv_covs, dets, chol, log_norm, ws, ws_bytes, s);
-    ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
-    ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
-#undef ABC_D
-  }
-  return set_error(ABC_ERR_UNSUPPORTED, "local_fit: d=%d", d);
+  int rc = ABC_OK;
+  if (!dispatch_int(LocalDims{}, d, [&](auto D) {
+        rc = launch_fit<D()>(X, w, N, nq, scaling, eps, covs, inv_covs, dets, chol, log_norm, ws,
+                             ws_bytes, s);
+      }))
+    return set_error(ABC_ERR_UNSUPPORTED, "local_fit: d=%d", d);
+  return rc;
 }
 
 extern "C" size_t abc_local_logpdf_workspace(int64_t M, int64_t N, int d) {
-  switch (d) {
-#define ABC_D(n) case n: return measure<PdfWs<n>>(M, N);
-    ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
-    ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
-#undef ABC_D
-  }
-  return Carver::SLACK;
+  size_t bytes = Carver::SLACK;
+  dispatch_int(LocalDims{}, d, [&](auto D) { bytes = measure<PdfWs<D()>>(M, N); });
+  return bytes;
 }
 
 extern "C" int abc_local_logpdf(const double* x, int64_t M, const double* X,
@@ -1671,11 +1666,10 @@ extern "C" int abc_local_logpdf(const double* x, int64_t M, const double* X,
     return local_wide_logpdf(x, M, X, w, N, d, inv_covs, log_norm, out, s);
   }
   ABC_CHECK_ARG(x && X && w && inv_covs && log_norm && out && ws, "local_logpdf: null pointer");
-  switch (d) {
-#define ABC_D(n) case n: return launch_pdf<n>(x, M, X, w, N, inv_covs, log_norm, out, ws, ws_bytes, s);
-    ABC_D(1) ABC_D(2) ABC_D(3) ABC_D(4) ABC_D(5) ABC_D(6) ABC_D(7) ABC_D(8)
-    ABC_D(9) ABC_D(10) ABC_D(11) ABC_D(12) ABC_D(13) ABC_D(14) ABC_D(15) ABC_D(16)
-#undef ABC_D
-  }
-  return set_error(ABC_ERR_UNSUPPORTED, "local_logpdf: d=%d", d);
+  int rc = ABC_OK;
+  if (!dispatch_int(LocalDims{}, d, [&](auto D) {
+        rc = launch_pdf<D()>(x, M, X, w, N, inv_covs, log_norm, out, ws, ws_bytes, s);
+      }))
+    return set_error(ABC_ERR_UNSUPPORTED, "local_logpdf: d=%d", d);
+  return rc;
 }

@@ -45,23 +45,6 @@ __device__ __forceinline__ unsigned long long dist_key(const double* __restrict_
   return (unsigned long long)__double_as_longlong(s);
 }
 
-// exclusive scan of one int per thread over the 256-thread block
-__device__ __forceinline__ int block_exscan(int v, int* sh, int& total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < WT; o <<= 1) {
-    const int a = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += a;
-    __syncthreads();
-  }
-  total = sh[WT - 1];
-  const int incl = sh[t];
-  __syncthreads();
-  return incl - v;
-}
-
 struct WideFitArgs {
   const double* X;
   const double* w;
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(WT) void local_wide_fit_kernel(WideFitArgs A) {
       const int64_t j = j0 + t;
       const int eq = (j < N && keys[j] == vs) ? 1 : 0;
       int tot;
-      const int before = block_exscan(eq, scan_sh, tot);
+      const int before = block_exscan<int, WT>(eq, scan_sh, tot);
       if (eq && seen + before == tie_rank) s_jcut = j + 1;   // (key, j) <= (v*, j*)
       seen += tot;
       if (seen > tie_rank) break;   // uniform: every thread holds the same seen
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(WT) void local_wide_fit_kernel(WideFitArgs A) {
         m = ((k < vs) || (k == vs && j < jcut)) && j != r0;
       }
       int tot;
-      const int pos = block_exscan(m, scan_sh, tot);
+      const int pos = block_exscan<int, WT>(m, scan_sh, tot);
       if (m) mem[cnt + pos] = (int32_t)j;
       cnt += tot;
     }

@@ -423,18 +423,13 @@ void launch_lse(const Plan& p, const T* A, const T* B, const double* m0,
                      p.tiles_per_chunk, p.groups, pm, pl, p.Mpad);
 }
 
+// K blocks (of 4 rank columns) mvn_lse_kernel is instantiated for
+using LseKBs = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 template <class T>
 int dispatch_lse(const Plan& p, const T* A, const T* B, const double* m0,
                  double* pm, double* pl, hipStream_t s) {
-  switch (p.KB) {
-#define ABC_KB(n) case n: launch_lse<T, n>(p, A, B, m0, pm, pl, s); break;
-    ABC_KB(1) ABC_KB(2) ABC_KB(3) ABC_KB(4) ABC_KB(5) ABC_KB(6) ABC_KB(7)
-    ABC_KB(8) ABC_KB(9) ABC_KB(10) ABC_KB(11) ABC_KB(12) ABC_KB(13)
-    ABC_KB(14) ABC_KB(15)
-#undef ABC_KB
-    default:
-      return set_error(ABC_ERR_UNSUPPORTED, "mvn_logpdf: r=%d too large", 4 * p.KB);
-  }
+  if (!dispatch_int(LseKBs{}, p.KB, [&](auto KB) { launch_lse<T, KB()>(p, A, B, m0, pm, pl, s); }))
+    return set_error(ABC_ERR_UNSUPPORTED, "mvn_logpdf: r=%d too large", 4 * p.KB);
   return ABC_OK;
 }
 

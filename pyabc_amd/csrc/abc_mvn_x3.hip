@@ -851,6 +851,9 @@ __global__ void x3_rescue_final(const int64_t* __restrict__ rescue,
   out[rescue[q0 + q]] = t > 0.0 ? log_const + LN2 * (mx + log2(t)) : -INFINITY;
 }
 
+// ranks pack_x3_kernel is instantiated for; any other r runs its runtime-r
+// instantiation RC = 0
+using PackRanks = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16>;
 template <int SIDE>
 void launch_pack(int r, dim3 grid, hipStream_t s, const double* P, const double* w,
                  int64_t n, int d, const double* mu, const double* U,
@@ -859,19 +862,12 @@ void launch_pack(int r, dim3 grid, hipStream_t s, const double* P, const double*
                  double* lw, int64_t Np, const int64_t* hint, float* cand_o,
                  int koff, const double* shift_dev = nullptr,
                  const unsigned int* count_dev = nullptr) {
-#define ABC_PACK_CASE(RC)                                                          \
-  case RC:                                                                         \
-    hipLaunchKernelGGL((pack_x3_kernel<SIDE, RC>), grid, dim3(128), 0, s, P, w, n, \
-                       d, mu, U, r, log_w_shift, K0pad, KB, hdr, img, ntiles, flags, \
-                       Y, lw, Np, hint, cand_o, koff, shift_dev, count_dev);       \
-    break;
-  switch (r) {
-    ABC_PACK_CASE(1) ABC_PACK_CASE(2) ABC_PACK_CASE(3) ABC_PACK_CASE(4)
-    ABC_PACK_CASE(5) ABC_PACK_CASE(6) ABC_PACK_CASE(7) ABC_PACK_CASE(8)
-    ABC_PACK_CASE(9) ABC_PACK_CASE(10) ABC_PACK_CASE(12) ABC_PACK_CASE(16)
-    default: ABC_PACK_CASE(0)
-  }
-#undef ABC_PACK_CASE
+  auto launch = [&](auto RC) {
+    hipLaunchKernelGGL((pack_x3_kernel<SIDE, RC()>), grid, dim3(128), 0, s, P, w, n, d, mu, U, r,
+                       log_w_shift, K0pad, KB, hdr, img, ntiles, flags, Y, lw, Np, hint, cand_o,
+                       koff, shift_dev, count_dev);
+  };
+  if (!dispatch_int(PackRanks{}, r, launch)) launch(std::integral_constant<int, 0>{});
 }
 
 // rows of the rescued candidates (x [M x d] -> xs [n x d]) and their
@@ -966,18 +962,15 @@ void launch_x3(const PlanX3& p, const half8* A, const half8* B, int koff,
                        p.tiles_per_chunk, p.groups, koff, p.KB0, po, pl, p.Mpad, count_dev);
 }
 
+// MFMA instructions per tile pair mvn_x3_kernel is instantiated for
+using X3KBs = std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11>;
 int dispatch_x3(const PlanX3& p, const half8* A, const half8* B, int koff,
                 double* po, double* pl, bool pass1, const unsigned int* count_dev,
                 hipStream_t s) {
-  switch (p.KB) {
-#define ABC_X3_CASE(K) \
-  case K: launch_x3<K, x3_ct(K)>(p, A, B, koff, po, pl, pass1, count_dev, s); break;
-    ABC_X3_CASE(2) ABC_X3_CASE(3) ABC_X3_CASE(4) ABC_X3_CASE(5) ABC_X3_CASE(6)
-    ABC_X3_CASE(7) ABC_X3_CASE(8) ABC_X3_CASE(9) ABC_X3_CASE(10) ABC_X3_CASE(11)
-#undef ABC_X3_CASE
-    default:
-      return set_error(ABC_ERR_UNSUPPORTED, "mvn x3: KB=%d unsupported", p.KB);
-  }
+  if (!dispatch_int(X3KBs{}, p.KB, [&](auto KB) {
+        launch_x3<KB(), x3_ct(KB())>(p, A, B, koff, po, pl, pass1, count_dev, s);
+      }))
+    return set_error(ABC_ERR_UNSUPPORTED, "mvn x3: KB=%d unsupported", p.KB);
   return ABC_OK;
 }
 static_assert(x3_kb(MAX_R) <= 11 && x3_kb(1) >= 2, "dispatch_x3 covers every rank");

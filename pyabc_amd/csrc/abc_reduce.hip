@@ -171,12 +171,6 @@ int wide_blocks(int64_t N, int d) {
 // Rows are strided over the grid; each thread keeps its row sums in
 // registers; blocks reduce by wave butterflies + LDS in fixed order (bitwise
 // reproducible); the final kernels reduce the block partials by a fixed tree.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // sum over the block of NV per-thread values -> out[0..NV) (thread 0 writes)
 template <int NV>
 __device__ __forceinline__ void block_sums(const double (&v)[NV], double* sh,
@@ -288,6 +282,8 @@ __global__ void mom2_expand(const double* __restrict__ tri, double* __restrict__
   out[2 + D + t] = tri[c] / out[0];
 }
 
+// the dimensions of the fast path; any other d takes the generic kernels
+using MomDims = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 10, 12, 16>;
 template <int D>
 void moments_fast(const double* X, const double* w, int64_t N, double* out,
                   double* p1, double* p2, double* pmax, double* tri, hipStream_t s) {
@@ -308,23 +304,6 @@ void moments_fast(const double* X, const double* w, int64_t N, double* out,
 // ---- scan -------------------------------------------------------------------
 constexpr int SCAN_T = 256, SCAN_I = 8, SCAN_TILE = SCAN_T * SCAN_I;
 
-__device__ double block_exclusive_scan(double v, double* sh, double& total) {
-  // Hillis-Steele over 256 threads in LDS (fixed order -> deterministic).
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < SCAN_T; o <<= 1) {
-    double add = (t >= o) ? sh[t - o] : 0.0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  total = sh[SCAN_T - 1];
-  double incl = sh[t];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(SCAN_T) void scan_tile_sums(
     const double* __restrict__ in, int64_t N, double* __restrict__ sums) {
   __shared__ double sh[SCAN_T];
@@ -333,7 +312,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_tile_sums(
   for (int k = 0; k < SCAN_I; ++k)
     if (base + k < N) s += in[base + k];
   double tot;
-  block_exclusive_scan(s, sh, tot);
+  block_exscan<double, SCAN_T>(s, sh, tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -347,7 +326,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_sums(double* __restrict__ sums,
   for (int64_t k = 0; k < per; ++k)
     if (b0 + k < n) s += sums[b0 + k];
   double tot;
-  double off = block_exclusive_scan(s, sh, tot);
+  double off = block_exscan<double, SCAN_T>(s, sh, tot);
   for (int64_t k = 0; k < per; ++k) {
     if (b0 + k < n) {
       double v = sums[b0 + k];
@@ -369,7 +348,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_apply(
     s += v[k];
   }
   double tot;
-  double run = block_exclusive_scan(s, sh, tot) + sums[blockIdx.x];
+  double run = block_exscan<double, SCAN_T>(s, sh, tot) + sums[blockIdx.x];
   for (int k = 0; k < SCAN_I; ++k) {
     run += v[k];
     if (base + k < N) out[base + k] = run;
@@ -487,14 +466,11 @@ extern "C" int abc_weighted_moments(const double* X, const double* w,
   ABC_CARVE(k, "moments", N, d);
   auto [p1, p2, pmax, tri] = k;
   hipStream_t s = as_stream(stream);
-  switch (d) {
-#define ABC_MOM_CASE(D) \
-    case D: moments_fast<D>(X, w, N, out, p1, p2, pmax, tri, s); ABC_LAUNCHED(); return ABC_OK;
-    ABC_MOM_CASE(1) ABC_MOM_CASE(2) ABC_MOM_CASE(3) ABC_MOM_CASE(4)
-    ABC_MOM_CASE(5) ABC_MOM_CASE(6) ABC_MOM_CASE(8) ABC_MOM_CASE(10)
-    ABC_MOM_CASE(12) ABC_MOM_CASE(16)
-#undef ABC_MOM_CASE
-    default: break;
+  if (dispatch_int(MomDims{}, d, [&](auto D) {
+        moments_fast<D()>(X, w, N, out, p1, p2, pmax, tri, s);
+      })) {
+    ABC_LAUNCHED();
+    return ABC_OK;
   }
   if (d > 64) {
     const int nb = wide_blocks(N, d);

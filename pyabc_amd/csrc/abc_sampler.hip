@@ -100,40 +100,25 @@ __global__ __launch_bounds__(256) void propose_wide_kernel(
   if (att_out) att_out[b] = used;
 }
 
-template <bool PPL>
-void launch_propose(int d, dim3 grid, hipStream_t s, const double* X,
+void launch_propose(bool per_particle_L, int d, dim3 grid, hipStream_t s, const double* X,
                     const double* cdf, const int32_t* guide, int64_t N, const double* L,
                     const int32_t* kind, const double* params, uint64_t seed,
                     uint32_t gen, int64_t idx0, int64_t B, int max_attempts,
                     double* theta, double* lp, int64_t* anc, int32_t* att) {
   const ProposalArgs A{X, cdf, guide, N, L, kind, params, d, max_attempts, seed, gen};
+  const int mode = proposal_mode(X, per_particle_L);
   if (d > 64) {
     const size_t lds = sizeof(double) * 2 * (size_t)d;
-    if (X == nullptr)
-      hipLaunchKernelGGL((propose_wide_kernel<PROP_PRIOR>), grid, dim3(256), lds, s, A, idx0, B,
+    dispatch_int(PropModes{}, mode, [&](auto MODE) {
+      hipLaunchKernelGGL((propose_wide_kernel<MODE()>), grid, dim3(256), lds, s, A, idx0, B,
                          theta, lp, anc, att);
-    else
-      hipLaunchKernelGGL((propose_wide_kernel<PPL ? PROP_LOCAL : PROP_MVN>), grid, dim3(256),
-                         lds, s, A, idx0, B, theta, lp, anc, att);
+    });
     return;
   }
-#define ABC_PROPOSE_CASE(DD)                                                        \
-  case DD:                                                                          \
-    if (X == nullptr)                                                               \
-      hipLaunchKernelGGL((propose_kernel<DD, PROP_PRIOR>), grid, dim3(256), 0, s, A, \
-                         idx0, B, theta, lp, anc, att);                             \
-    else                                                                            \
-      hipLaunchKernelGGL((propose_kernel<DD, PPL ? PROP_LOCAL : PROP_MVN>), grid,    \
-                         dim3(256), 0, s, A, idx0, B, theta, lp, anc, att);         \
-    break;
-  switch (d) {
-    ABC_PROPOSE_CASE(1) ABC_PROPOSE_CASE(2) ABC_PROPOSE_CASE(3)
-    ABC_PROPOSE_CASE(4) ABC_PROPOSE_CASE(5) ABC_PROPOSE_CASE(6)
-    ABC_PROPOSE_CASE(8) ABC_PROPOSE_CASE(10) ABC_PROPOSE_CASE(12)
-    ABC_PROPOSE_CASE(16)
-    default: ABC_PROPOSE_CASE(0)
-  }
-#undef ABC_PROPOSE_CASE
+  dispatch_candidate(d, mode, [&](auto D, auto MODE) {
+    hipLaunchKernelGGL((propose_kernel<D(), MODE()>), grid, dim3(256), 0, s, A, idx0, B, theta,
+                       lp, anc, att);
+  });
 }
 
 __global__ void prior_logpdf_kernel(const double* __restrict__ th, int64_t B,
@@ -183,78 +168,30 @@ __global__ __launch_bounds__(256) void simulate_lg_kernel(
   }
 }
 
-// ---- PNormDistance (pterm / pnorm_acc: abc_candidate.h) -------------------
+// ---- PNormDistance (pnorm_row / pnorm_wave_rows: abc_candidate.h) ----------
 
+// S <= 32: one thread per row
 __global__ __launch_bounds__(256) void pnorm_row_kernel(
     const double* __restrict__ x, int64_t B, int S,
     const double* __restrict__ x0, const double* __restrict__ wf, double p,
     double* __restrict__ d) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const double* xr = x + b * S;
-  double s = 0.0;
-  if (isinf(p)) {
-    for (int k = 0; k < S; ++k) s = fmax(s, fabs(wf[k] * (xr[k] - x0[k])));
-    d[b] = s;
-  } else {
-    for (int k = 0; k < S; ++k) s += pterm(fabs(wf[k] * (xr[k] - x0[k])), p);
-    d[b] = (p == 1.0) ? s : (p == 2.0 ? sqrt(s) : pow(s, 1.0 / p));
-  }
+  d[b] = pnorm_row(x + b * S, S, x0, wf, p);
 }
 
-// wide rows: lanes stride over k (coalesced), each wave takes PW_ROWS rows at
-// once so that many row loads are in flight per lane (one row per wave left
-// the HBM stream latency-bound at ~40% of peak).  Per row the order of the
-// sum is unchanged: lane-strided partials, then the wave tree.
-constexpr int PW_ROWS = 8;
+// wide rows: PNORM_ROWS rows per wave, four waves per block
 __global__ __launch_bounds__(256) void pnorm_wave_kernel(
     const double* __restrict__ x, int64_t B, int S,
     const double* __restrict__ x0, const double* __restrict__ wf, double p,
     double* __restrict__ d) {
-  const int lane = threadIdx.x & 63;
-  const int64_t b0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * PW_ROWS;
+  const int64_t b0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * PNORM_ROWS;
   if (b0 >= B) return;  // whole wave
-  const bool inf = isinf(p);
-  double s[PW_ROWS];
-#pragma unroll
-  for (int r = 0; r < PW_ROWS; ++r) s[r] = 0.0;
-  for (int k = lane; k < S; k += 64) {
-    const double wk = wf[k], ck = x0[k];
-    double v[PW_ROWS];
-#pragma unroll
-    for (int r = 0; r < PW_ROWS; ++r) v[r] = b0 + r < B ? x[(b0 + r) * S + k] : ck;
-#pragma unroll
-    for (int r = 0; r < PW_ROWS; ++r) {
-      const double a = fabs(wk * (v[r] - ck));
-      s[r] = inf ? fmax(s[r], a) : s[r] + pterm(a, p);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < PW_ROWS; ++r) {
-    const double t = inf ? wave_max(s[r]) : wave_sum(s[r]);
-    if (lane == 0 && b0 + r < B)
-      d[b0 + r] = inf ? t : ((p == 1.0) ? t : (p == 2.0 ? sqrt(t) : pow(t, 1.0 / p)));
-  }
+  pnorm_wave_rows(x, b0, B, S, x0, wf, p, [&](int r, double dist) { d[b0 + r] = dist; });
 }
 
 // ---- order-preserving accept compaction ------------------------------------
 constexpr int CT_T = 256, CT_I = 8, CT_TILE = CT_T * CT_I;
-
-__device__ int64_t block_exscan_i64(int64_t v, int64_t* sh, int64_t& total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < CT_T; o <<= 1) {
-    int64_t add = (t >= o) ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  total = sh[CT_T - 1];
-  int64_t incl = sh[t];
-  __syncthreads();
-  return incl - v;
-}
 
 __global__ __launch_bounds__(CT_T) void accept_count_kernel(
     const double* __restrict__ d, int64_t B, double eps,
@@ -265,7 +202,7 @@ __global__ __launch_bounds__(CT_T) void accept_count_kernel(
   for (int k = 0; k < CT_I; ++k)
     if (base + k < B && d[base + k] <= eps) ++c;
   int64_t tot;
-  block_exscan_i64(c, sh, tot);
+  block_exscan<int64_t, CT_T>(c, sh, tot);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
 
@@ -278,7 +215,7 @@ __global__ __launch_bounds__(CT_T) void accept_scan_kernel(
   for (int64_t k = 0; k < per; ++k)
     if (b0 + k < n) s += tile_cnt[b0 + k];
   int64_t tot;
-  int64_t off = block_exscan_i64(s, sh, tot);
+  int64_t off = block_exscan<int64_t, CT_T>(s, sh, tot);
   for (int64_t k = 0; k < per; ++k)
     if (b0 + k < n) { int64_t v = tile_cnt[b0 + k]; tile_cnt[b0 + k] = off; off += v; }
   if (threadIdx.x == 0) *count = tot;
@@ -293,7 +230,7 @@ __global__ __launch_bounds__(CT_T) void accept_write_kernel(
   for (int k = 0; k < CT_I; ++k)
     if (base + k < B && d[base + k] <= eps) ++c;
   int64_t tot;
-  int64_t pos = block_exscan_i64(c, sh, tot) + tile_off[blockIdx.x];
+  int64_t pos = block_exscan<int64_t, CT_T>(c, sh, tot) + tile_off[blockIdx.x];
   for (int k = 0; k < CT_I; ++k)
     if (base + k < B && d[base + k] <= eps) idx[pos++] = base + k;
 }
@@ -343,9 +280,9 @@ extern "C" int abc_propose(const double* X, const double* cdf,
   if (B == 0) return ABC_OK;
   ABC_CHECK_ARG(theta && prior_logpdf && prior_kind && prior_params, "propose: null pointer");
   ABC_CHECK_ARG(X == nullptr || (cdf && L && N >= 1), "propose: population needs cdf, L, N");
-  launch_propose<false>(d, dim3((unsigned)ceil_div(B, 256)), as_stream(stream), X, cdf,
-                        guide, N, L, prior_kind, prior_params, seed, generation, idx0, B,
-                        max_attempts, theta, prior_logpdf, ancestor, attempts);
+  launch_propose(false, d, dim3((unsigned)ceil_div(B, 256)), as_stream(stream), X, cdf, guide,
+                 N, L, prior_kind, prior_params, seed, generation, idx0, B, max_attempts, theta,
+                 prior_logpdf, ancestor, attempts);
   ABC_LAUNCHED();
   return ABC_OK;
 }
@@ -364,9 +301,9 @@ extern "C" int abc_local_propose(const double* X, const double* cdf,
   if (B == 0) return ABC_OK;
   ABC_CHECK_ARG(X && cdf && chol && N >= 1 && theta && prior_logpdf && prior_kind &&
                 prior_params, "local_propose: null pointer");
-  launch_propose<true>(d, dim3((unsigned)ceil_div(B, 256)), as_stream(stream), X, cdf,
-                       guide, N, chol, prior_kind, prior_params, seed, generation, idx0, B,
-                       max_attempts, theta, prior_logpdf, ancestor, attempts);
+  launch_propose(true, d, dim3((unsigned)ceil_div(B, 256)), as_stream(stream), X, cdf, guide,
+                 N, chol, prior_kind, prior_params, seed, generation, idx0, B, max_attempts,
+                 theta, prior_logpdf, ancestor, attempts);
   ABC_LAUNCHED();
   return ABC_OK;
 }
@@ -422,7 +359,7 @@ extern "C" int abc_pnorm(const double* x, int64_t B, int S, const double* x0,
     hipLaunchKernelGGL(pnorm_row_kernel, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0,
                        as_stream(stream), x, B, S, x0, wf, p, d);
   else
-    hipLaunchKernelGGL(pnorm_wave_kernel, dim3((unsigned)ceil_div(B, 4 * PW_ROWS)), dim3(256), 0,
+    hipLaunchKernelGGL(pnorm_wave_kernel, dim3((unsigned)ceil_div(B, 4 * PNORM_ROWS)), dim3(256), 0,
                        as_stream(stream), x, B, S, x0, wf, p, d);
   ABC_LAUNCHED();
   return ABC_OK;

@@ -139,21 +139,6 @@ __global__ __launch_bounds__(RT) void radix_scatter_kernel(
 // ---- generic exclusive scan of int64 (3 phases) -----------------------------
 constexpr int ST = 256, SI = 8, STILE = ST * SI;
 
-__device__ int64_t block_exscan(int64_t v, int64_t* sh, int64_t& total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < ST; o <<= 1) {
-    int64_t add = (t >= o) ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  total = sh[ST - 1];
-  int64_t incl = sh[t];
-  __syncthreads();
-  return incl - v;
-}
 __global__ __launch_bounds__(ST) void exscan_sums(const int64_t* __restrict__ in,
                                                   int64_t n,
                                                   int64_t* __restrict__ sums) {
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(ST) void exscan_sums(const int64_t* __restrict__ in
   int64_t s = 0;
   for (int k = 0; k < SI; ++k) if (b + k < n) s += in[b + k];
   int64_t tot;
-  block_exscan(s, sh, tot);
+  block_exscan<int64_t, ST>(s, sh, tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(ST) void exscan_top(int64_t* __restrict__ sums,
@@ -173,7 +158,7 @@ __global__ __launch_bounds__(ST) void exscan_top(int64_t* __restrict__ sums,
   int64_t s = 0;
   for (int64_t k = 0; k < per; ++k) if (b0 + k < n) s += sums[b0 + k];
   int64_t tot;
-  int64_t off = block_exscan(s, sh, tot);
+  int64_t off = block_exscan<int64_t, ST>(s, sh, tot);
   for (int64_t k = 0; k < per; ++k)
     if (b0 + k < n) { int64_t v = sums[b0 + k]; sums[b0 + k] = off; off += v; }
 }
@@ -187,7 +172,7 @@ __global__ __launch_bounds__(ST) void exscan_apply(const int64_t* __restrict__ i
   int64_t s = 0;
   for (int k = 0; k < SI; ++k) { v[k] = (b + k < n) ? in[b + k] : 0; s += v[k]; }
   int64_t tot;
-  int64_t run = block_exscan(s, sh, tot) + sums[blockIdx.x];
+  int64_t run = block_exscan<int64_t, ST>(s, sh, tot) + sums[blockIdx.x];
   for (int k = 0; k < SI; ++k) { if (b + k < n) out[b + k] = run; run += v[k]; }
 }
 
