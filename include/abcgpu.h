@@ -485,16 +485,44 @@ int abc_local_fit(const double* X, const double* w, int64_t N, int d,
                   int64_t k, double scaling, double eps, double* covs,
                   double* inv_covs, double* dets, double* chol,
                   double* log_norm, void* ws, size_t ws_bytes, void* stream);
+/* The path the last abc_local_fit on the calling thread took: host state,
+ * no device work, 0 before the first fit and for d > 16.  Tests read it so
+ * that a case meant for one moments path cannot pass by falling back to
+ * another.  Bit flags: */
+#define ABC_FIT_KNN 1             /* fp32-MFMA k-NN select ran (N >= 2048)        */
+#define ABC_FIT_LIST 2            /* list mode: the select summed the moments     */
+#define ABC_FIT_DENSE 4           /* f16-limb moments GEMM ran (d <= 5, 16 k > N) */
+#define ABC_FIT_DEFER 8           /* ... with the deferred collect                */
+#define ABC_FIT_DENSE_REJECTED 16 /* its rounding guard flagged a particle: the
+                                   * fit came from the fp64 VALU moments sweep    */
+#define ABC_FIT_SELECT_FALLBACK 32 /* a deferred-collect queue or bracket failed:
+                                    * the select ran again with its own collect  */
+int abc_local_fit_route(void);
 /* pdf: out[i] = log( sum_j w_j exp(-d_ij^T inv_j d_ij / 2 - log_norm_j)
  * / sum_j w_j ), d_ij = X_j - x_i.  d <= 16: the quadratic form is a GEMM
  * over the candidates' quadratic features on fp64 MFMA (workspace: packed
  * population coefficients + per-chunk partial sums); 16 < d <= 64: a direct
- * fp64 quadratic form per pair (no workspace). */
+ * fp64 quadratic form per pair (no workspace).  The GEMM expands the form in
+ * coordinates centred at X[0] and cancels terms as large as T_i = (U + V
+ * |x_i - X_0|)^2, U = max_j sqrt|inv_j|_F |X_j - X_0|, V = max_j
+ * sqrt|inv_j|_F; a candidate for which the rounding that leaves in q / 2,
+ * (K + d + 4) / 2 eps T_i with K = d (d + 1) / 2 + d + 1, is above 1e-6
+ * (thin ridges with far-apart modes, a stray particle at row 0, a candidate
+ * far from row 0) is answered by the direct form instead: decided per
+ * candidate on the device, no host synchronisation, several times slower. */
 size_t abc_local_logpdf_workspace(int64_t M, int64_t N, int d);
 int abc_local_logpdf(const double* x, int64_t M, const double* X,
                      const double* w, int64_t N, int d, const double* inv_covs,
                      const double* log_norm, double* out, void* ws,
                      size_t ws_bytes, void* stream);
+/* How the last abc_local_logpdf that used this workspace with the same
+ * (M, N, d) was answered: *direct = the number of candidates that took the
+ * direct form (M at d > 16), *bound = the bound on the GEMM's error in q / 2
+ * for a candidate at X[0] (the population's share of it).  Reads three
+ * doubles back from the workspace: synchronises the stream.  For tests and
+ * diagnostics. */
+int abc_local_logpdf_route(int64_t M, int64_t N, int d, void* ws, size_t ws_bytes,
+                           void* stream, int64_t* direct, double* bound);
 /* rvs: ancestor j ~ Cat(w) (cdf), theta = X_j + chol_j n; same Philox keying
  * and prior re-draw loop as abc_propose. */
 int abc_local_propose(const double* X, const double* cdf,

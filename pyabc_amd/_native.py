@@ -80,8 +80,10 @@ SIGNATURES = {
     "abc_local_fit_workspace": (SZ, [I64, I32]),
     "abc_local_fit": (I32, [P, P, I64, I32, I64, D, D, P, P, P, P, P, P, SZ,
                             P]),
+    "abc_local_fit_route": (I32, []),
     "abc_local_logpdf_workspace": (SZ, [I64, I64, I32]),
     "abc_local_logpdf": (I32, [P, I64, P, P, I64, I32, P, P, P, P, SZ, P]),
+    "abc_local_logpdf_route": (I32, [I64, I64, I32, P, SZ, P, P, P]),
     "abc_local_propose": (I32, [P, P, P, I64, I32, P, P, P, U64, U32, I64,
                                 I64, I32, P, P, P, P, P]),
     "abc_bootstrap_cv_workspace": (SZ, [I64]),
@@ -126,6 +128,8 @@ ABC_COMM_ID_BYTES = 128
 ABC_COMM_F64, ABC_COMM_I64 = 0, 1
 ABC_COMM_SUM, ABC_COMM_MAX, ABC_COMM_MIN = 0, 1, 2
 ABC_PROF_DENSITY, ABC_PROF_CANDIDATES, ABC_PROF_REGEN, ABC_PROF_RESCUE = 0, 1, 2, 3
+(ABC_FIT_KNN, ABC_FIT_LIST, ABC_FIT_DENSE, ABC_FIT_DEFER, ABC_FIT_DENSE_REJECTED,
+ ABC_FIT_SELECT_FALLBACK) = 1, 2, 4, 8, 16, 32
 ABC_PREC_F64 = 0
 ABC_PREC_F32 = 1
 ABC_PREC_X3 = 2

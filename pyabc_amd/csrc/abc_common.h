@@ -241,6 +241,23 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
+// LocalTransition density, d <= 16: whether candidate xi is answered by the
+// direct-difference form instead of the MFMA expansion about X_0 (abc_local.hip,
+// LOCAL_PDF_LIMIT).  uv = [U, V] = max_j sqrt|A_j|_F [|X_j - X_0|, 1]: the
+// expansion's terms for (i, j) are no larger than (U + V |x_i - X_0|)^2.  One
+// definition with explicit fma: the kernels of both translation units that
+// evaluate it must agree on every candidate.
+__device__ __forceinline__ bool local_pdf_direct(const double* xi, const double* X0, int d,
+                                                 const double* uv, double tmax) {
+  double s = 0.0;
+  for (int a = 0; a < d; ++a) {
+    const double y = xi[a] - X0[a];
+    s = __builtin_fma(y, y, s);
+  }
+  const double r = __builtin_fma(uv[1], sqrt(s), uv[0]);
+  return !(r * r <= tmax);   // (NaN: direct)
+}
+
 // ---- block helpers -----------------------------------------------------------
 // Exclusive scan of one value per thread over a block of NT threads:
 // Hillis-Steele in LDS (sh[NT]), fixed order, so deterministic for doubles

@@ -20,6 +20,13 @@
 #include "abc_common.h"
 
 namespace abc {
+// direct-difference density for a runtime d (abc_local_wide.hip): d > 16, and
+// behind the MFMA route at d <= 16 for the candidates local_pdf_direct(uv,
+// tmax) names
+int local_wide_logpdf(const double* x, int64_t M, const double* X, const double* w,
+                      int64_t N, int d, const double* inv, const double* lnorm,
+                      double* out, hipStream_t s, const double* uv = nullptr,
+                      double tmax = 0.0);
 namespace {
 
 constexpr double LOG_2PI = 1.8378770664093454836;
@@ -625,20 +632,77 @@ __global__ __launch_bounds__(256) void local_moments_kernel(
   }
 }
 
+// Every moments path hands local_finish_kernel sums about the particle X_n,
+// and cov = S2 / sw - mean mean^T loses (1 + m2) eps in the metric of C, m2 =
+// mean^T C^-1 mean the whitened squared distance of the particle from the
+// mean of its neighbours: ~10 at the far end of a ridge, 1e2..1e4 for the
+// sparse tail of a population at small k, 1e6 and far more for a stray
+// particle whose neighbours all lie off to one side.  Above this loss -- or
+// when the one-sweep covariance came out with det <= 0 and the EPS loop had
+// to run -- the particle is queued for local_recentre_kernel, which sums its
+// moments again about that mean (np.cov's own second pass).
+constexpr double LOCAL_OFFCENTRE_LOSS = 1e-10;
+constexpr double F64_EPS = 2.220446049250313e-16;  // fp64 epsilon
+
+// The reference's fix-ups and factorisations of one particle's covariance
+// (local_transition.py:112-139) and its five outputs.  cov comes in unscaled
+// and leaves as written; returns how often "cov += eps I" ran.
+template <int D>
+__device__ __forceinline__ int local_factor_write(
+    double (&cov)[D][D], double (&inv)[D][D], const double* __restrict__ X, double scaling,
+    double eps, int64_t n, double* __restrict__ covs, double* __restrict__ invs,
+    double* __restrict__ dets, double* __restrict__ chol, double* __restrict__ lnorm) {
+  double csum = 0.0;
+  for (int a = 0; a < D; ++a)
+    for (int b = 0; b < D; ++b) csum += cov[a][b];
+  if (fabs(csum) == 0.0)
+    for (int a = 0; a < D; ++a) cov[a][a] = fabs(X[a]);  // X[0, a]
+  for (int a = 0; a < D; ++a)
+    for (int b = 0; b < D; ++b) cov[a][b] *= scaling;
+  double lu[D][D];
+  int perm[D];
+  double det;
+  int it = 0;
+  for (;; ++it) {
+    for (int a = 0; a < D; ++a)
+      for (int b = 0; b < D; ++b) lu[a][b] = cov[a][b];
+    det = lu_factor<D>(lu, perm);
+    if (!(det <= 0.0) || it >= 1000000) break;  // NaN exits, as "while det <= 0" does
+    for (int a = 0; a < D; ++a) cov[a][a] += eps;
+  }
+  double L[D][D];
+  lu_inverse<D>(lu, perm, inv);
+  cholesky<D>(cov, L);
+  for (int a = 0; a < D; ++a)
+    for (int b = 0; b < D; ++b) {
+      covs[n * D * D + a * D + b] = cov[a][b];
+      invs[n * D * D + a * D + b] = inv[a][b];
+      chol[n * D * D + a * D + b] = L[a][b];
+    }
+  dets[n] = det;
+  lnorm[n] = 0.5 * (D * LOG_2PI + log(det));
+  return it;
+}
+
 // Per particle: the moments (partials added in chunk order), then the
-// reference's fix-ups and factorisations (local_transition.py:112-139).
+// fix-ups and factorisations.  Particles to be summed again are appended to
+// queue (*qcount of them; zeroed by the caller): their outputs are written
+// here too and overwritten by local_recentre_kernel.
 template <int D>
 __global__ __launch_bounds__(256) void local_finish_kernel(
     const double* __restrict__ X, int64_t N, int64_t nq, double scaling, double eps,
     const double* __restrict__ part, int RS, double* __restrict__ covs,
     double* __restrict__ invs, double* __restrict__ dets,
     double* __restrict__ chol, double* __restrict__ lnorm,
-    const int* __restrict__ done, const double* __restrict__ lmom) {
+    const int* __restrict__ done, const double* __restrict__ lmom,
+    int* __restrict__ queue, int* __restrict__ qcount) {
   constexpr int NM = local_nm<D>();
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const bool listed = done && done[n];   // moments summed by knn_select_kernel
   double cov[D][D];
+  double mean[D];
+  bool centred = false;   // cov is the np.cov branch: S2 / sw - mean mean^T
   if (N == 1) {
     // indices is 1-D -> deltas = |X|, one sample -> diag(|X[0]|)
     for (int a = 0; a < D; ++a)
@@ -668,41 +732,108 @@ __global__ __launch_bounds__(256) void local_finish_kernel(
       // sum a (d - dbar)(d - dbar)^T / (1 - sum a^2)
       const double sw = M[0];
       const double sa2 = M[1] / (sw * sw);
-      double mean[D];
       for (int a = 0; a < D; ++a) mean[a] = M[2 + a] / sw;
       for (int a = 0; a < D; ++a)
         for (int b = 0; b < D; ++b)
           cov[a][b] = (S2[a][b] / sw - mean[a] * mean[b]) / (1.0 - sa2);
+      centred = true;
     }
   }
-  double csum = 0.0;
+  double inv[D][D];
+  const int fired = local_factor_write<D>(cov, inv, X, scaling, eps, n, covs, invs, dets, chol, lnorm);
+  if (!centred) return;
+  // mean^T C^-1 mean (inv is the inverse of scaling * C); a negative form
+  // says the one-sweep covariance was not positive definite.  The EPS loop is
+  // looked at on its own: a covariance it regularised has a tame inverse.
+  double m2 = 0.0;
   for (int a = 0; a < D; ++a)
-    for (int b = 0; b < D; ++b) csum += cov[a][b];
-  if (fabs(csum) == 0.0)
-    for (int a = 0; a < D; ++a) cov[a][a] = fabs(X[a]);  // X[0, a]
-  for (int a = 0; a < D; ++a)
-    for (int b = 0; b < D; ++b) cov[a][b] *= scaling;
-  double lu[D][D];
-  int perm[D];
-  double det;
-  for (int it = 0;; ++it) {
+    for (int b = 0; b < D; ++b) m2 += mean[a] * inv[a][b] * mean[b];
+  m2 *= scaling;
+  if (fired > 0 || (1.0 + m2) * F64_EPS > LOCAL_OFFCENTRE_LOSS || m2 < 0.0)
+    queue[atomicAdd(qcount, 1)] = (int)n;
+}
+
+// sum of one value per thread over a block of 256, fixed tree (deterministic)
+__device__ __forceinline__ double block_sum256(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// The queued particles' second pass, one block per particle (blocks stride
+// the queue; all exit at once when it is empty): the membership sweep of
+// local_moments_kernel over all rows, first for the neighbours' weighted
+// mean, then for the moments of e = X_j - c about c = X_n + mean -- e is
+// small and nearly exact, and its residual mean (rounding of c) is taken
+// out.  Thread 0 redoes the fix-ups and factorisations.
+template <int D>
+__global__ __launch_bounds__(256) void local_recentre_kernel(
+    const double* __restrict__ X, const double* __restrict__ w, int64_t N, double scaling,
+    double eps, const unsigned long long* __restrict__ sel_v,
+    const long long* __restrict__ sel_jcut, const long long* __restrict__ sel_rank0,
+    const int* __restrict__ queue, const int* __restrict__ qcount, double* __restrict__ covs,
+    double* __restrict__ invs, double* __restrict__ dets, double* __restrict__ chol,
+    double* __restrict__ lnorm) {
+  __shared__ double sh[256];
+  const int cnt = *qcount;
+  for (int q = blockIdx.x; q < cnt; q += gridDim.x) {
+    const int64_t n = queue[q];
+    double xp[D];
+    for (int a = 0; a < D; ++a) xp[a] = X[n * D + a];
+    const unsigned long long vs = sel_v[n];
+    const long long jcut = sel_jcut[n], r0 = sel_rank0[n];
+    auto member = [&](int64_t j, double (&xj)[D]) {
+      for (int a = 0; a < D; ++a) xj[a] = X[j * D + a];
+      const unsigned long long key = (unsigned long long)__double_as_longlong(dist2v<D>(xj, xp));
+      return (key < vs || (key == vs && j < jcut)) && j != r0;
+    };
+    double t0 = 0.0, t1 = 0.0, c[D];
+    for (int a = 0; a < D; ++a) c[a] = 0.0;
+    for (int64_t j = threadIdx.x; j < N; j += 256) {
+      double xj[D];
+      if (!member(j, xj)) continue;
+      const double lw = w[j];
+      t0 += lw;
+      t1 += lw * lw;
+      for (int a = 0; a < D; ++a) c[a] += lw * (xj[a] - xp[a]);
+    }
+    const double sw = block_sum256(t0, sh);
+    const double sa2 = block_sum256(t1, sh) / (sw * sw);
+    for (int a = 0; a < D; ++a) c[a] = xp[a] + block_sum256(c[a], sh) / sw;
+    double s1[D], s2[D][D];
+    for (int a = 0; a < D; ++a) {
+      s1[a] = 0.0;
+      for (int b = 0; b < D; ++b) s2[a][b] = 0.0;
+    }
+    for (int64_t j = threadIdx.x; j < N; j += 256) {
+      double xj[D];
+      if (!member(j, xj)) continue;
+      const double lw = w[j];
+      double e[D];
+      for (int a = 0; a < D; ++a) e[a] = xj[a] - c[a];
+      for (int a = 0; a < D; ++a) {
+        s1[a] += lw * e[a];
+        for (int b = a; b < D; ++b) s2[a][b] += lw * e[a] * e[b];
+      }
+    }
+    for (int a = 0; a < D; ++a) s1[a] = block_sum256(s1[a], sh) / sw;
+    double cov[D][D];
     for (int a = 0; a < D; ++a)
-      for (int b = 0; b < D; ++b) lu[a][b] = cov[a][b];
-    det = lu_factor<D>(lu, perm);
-    if (!(det <= 0.0) || it >= 1000000) break;  // NaN exits, as "while det <= 0" does
-    for (int a = 0; a < D; ++a) cov[a][a] += eps;
-  }
-  double inv[D][D], L[D][D];
-  lu_inverse<D>(lu, perm, inv);
-  cholesky<D>(cov, L);
-  for (int a = 0; a < D; ++a)
-    for (int b = 0; b < D; ++b) {
-      covs[n * D * D + a * D + b] = cov[a][b];
-      invs[n * D * D + a * D + b] = inv[a][b];
-      chol[n * D * D + a * D + b] = L[a][b];
+      for (int b = a; b < D; ++b) {
+        const double v = (block_sum256(s2[a][b], sh) / sw - s1[a] * s1[b]) / (1.0 - sa2);
+        cov[a][b] = v;
+        cov[b][a] = v;
+      }
+    if (threadIdx.x == 0) {
+      double inv[D][D];
+      local_factor_write<D>(cov, inv, X, scaling, eps, n, covs, invs, dets, chol, lnorm);
     }
-  dets[n] = det;
-  lnorm[n] = 0.5 * (D * LOG_2PI + log(det));
+  }
 }
 
 // row chunks of the moments kernel: ~8 waves per SIMD, >= 64 rows a chunk
@@ -730,10 +861,16 @@ inline int moments_chunks(int64_t N) {
 // f32 accumulation is exact; every 256 steps (8192 rows) the sums are added
 // into fp64 partials (integers, exact).  The only rounding is the last
 // limb's (2^(e_f - 56) per term) and the fp64 re-centring at X_n
-// (mm_finish_kernel), whose error bound is checked per particle against the
-// local variance: a particle that fails it sends the whole fit back to the
-// VALU kernel (a device flag read by the host; never seen on the tests'
-// populations).
+// (mm_finish_kernel), whose error bound -- sized by |X_n - X_0|^2 -- is
+// checked per particle against 1e-11 of its local diagonal variance: a
+// particle that fails it sends the whole fit back to the VALU kernel (a
+// device flag read by the host, ABC_FIT_DENSE_REJECTED in
+// abc_local_fit_route).  The diagonal is not the thin direction of a rotated
+// ridge, so the check does not bound the error Sigma^-1 sees; the bound is
+// pessimistic enough that, measured, fits it lets through stay within 12x of
+// the float64 oracle's own whitened error up to cond 1e8 (the tests allow
+// 16x), and populations with modes 30 apart or a stray row 0 are rejected
+// (tests/test_gpu_local_conditioning.py).
 constexpr int ML_NL = 5;
 template <int D> constexpr int mm_nc() { return local_nm<D>() * ML_NL; }
 template <int D> constexpr int mm_nt() { return (mm_nc<D>() + 15) / 16; }
@@ -1159,6 +1296,9 @@ struct FitWs {
   }
 };
 
+// abc_local_fit_route(): the path the last abc_local_fit on this thread took
+thread_local int g_fit_route = 0;
+
 template <int D>
 int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                double scaling, double eps, double* covs, double* inv,
@@ -1188,6 +1328,7 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
   // dense k after the k-NN select's count sweep: the moments sweep does the
   // collect (deferred collect, abc_local_dense.h) -- one sweep less
   const bool defer = knn && !list_ok && dense;
+  g_fit_route = (knn ? ABC_FIT_KNN : 0) | (list_ok ? ABC_FIT_LIST : 0);
   // (null without the k-NN select, as the kernels below expect)
   int* done = knn ? k.done : nullptr;
   double* lmom = knn ? k.lmom : nullptr;
@@ -1251,6 +1392,7 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
     ABC_LAUNCHED();
     int h_flag = 0;
     bool finished = false;   // mm_finish ran already (deferred collect)
+    g_fit_route |= ABC_FIT_DENSE;
     if (knn) {
       // membership from the centred fp32 keys of the k-NN select
       const int64_t nrows = (nsteps + DM_SB) * 32;
@@ -1295,9 +1437,11 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                              sel_v, sel_ties, sel_rank0, (const int*)k.need);
           ABC_LAUNCHED();
           plain = true;
+          g_fit_route |= ABC_FIT_SELECT_FALLBACK;
         } else {
           h_flag = h_f[0];
           finished = true;
+          g_fit_route |= ABC_FIT_DEFER;
         }
       }
       if (plain) {
@@ -1325,6 +1469,7 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
     }
     if (h_flag) {
       dense = false;   // rounding bound not met somewhere: the VALU kernel
+      g_fit_route |= ABC_FIT_DENSE_REJECTED;
     } else {
       mom = cenm;
       mom_rs = 1;
@@ -1336,10 +1481,18 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
                          list_ok ? (const int*)done : nullptr);
     ABC_LAUNCHED();
   }
+  // (the select's need flags and counters are dead by now: the re-centring
+  // queue and its length)
+  ABC_HIP(hipMemsetAsync(k.cnt, 0, 2 * sizeof(int), s));
   hipLaunchKernelGGL((local_finish_kernel<D>), dim3((unsigned)ceil_div(N, 256)), dim3(256),
                      0, s, X, N, nq, scaling, eps, mom, mom_rs, covs, inv,
                      dets, chol, lnorm, (const int*)(list_ok ? done : nullptr),
-                     (const double*)lmom);
+                     (const double*)lmom, k.need, k.cnt);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL((local_recentre_kernel<D>), dim3((unsigned)(N < 256 ? N : 256)), dim3(256),
+                     0, s, X, w, N, scaling, eps, (const unsigned long long*)sel_v,
+                     (const long long*)sel_ties, (const long long*)sel_rank0,
+                     (const int*)k.need, (const int*)k.cnt, covs, inv, dets, chol, lnorm);
   ABC_LAUNCHED();
   return ABC_OK;
 }
@@ -1358,11 +1511,26 @@ int launch_fit(const double* X, const double* w, int64_t N, int64_t nq,
 // (population rows = A operand, candidate columns = B operand), followed by
 // the running max / exp2 / sum over j of each candidate column (exp2 on the
 // f32 unit, 1e-7 per term).
+//
+// The expansion cancels: its K0 terms are as large as T_ij = |A_j|_F (|Y_j| +
+// |y_i|)^2 and sum to q ~ d, so q_ij / 2 carries up to (K0 + d + 4) / 2
+// roundings of eps T_ij -- nothing for a compact, well-conditioned population
+// (T ~ 1e3), but past the density's 2e-6 on a thin ridge with far-apart modes,
+// when row 0 is a stray particle, or for a candidate far from row 0.  The
+// guard kernel reduces U = max_j sqrt|A_j|_F |Y_j| and V = max_j sqrt|A_j|_F
+// on the device, so that T_ij <= (U + V |y_i|)^2 for every j; a candidate
+// whose bound is above LOCAL_PDF_LIMIT is left out by the combine kernel and
+// answered by local_wide_pdf_kernel (direct differences X_j - x_i, runtime
+// d, no cancellation), which is enqueued behind it and whose blocks exit at
+// once where no candidate needs them.  No host read decides anything.
+constexpr double LOCAL_PDF_LIMIT = 1e-6;   // bound on the error of q / 2 the MFMA route may carry
 template <int D>
 struct LocalFeat {
   static constexpr int K0 = D * (D + 1) / 2 + D + 1;
   static constexpr int KB = (K0 + 3) / 4;          // MFMA k-blocks of 4
   static constexpr int NT = KB <= 6 ? 4 : (KB <= 16 ? 2 : 1);  // candidate tiles per wave
+  // largest bound (U + V |y_i|)^2 the MFMA route answers
+  static constexpr double TMAX = LOCAL_PDF_LIMIT / (0.5 * (K0 + D + 4) * 2.220446049250313e-16);
 };
 
 // feature k of centred candidate y (order: a <= b pairs, linear, constant)
@@ -1444,6 +1612,38 @@ __global__ __launch_bounds__(256) void local_pack_kernel(
   psi[e] = v;
 }
 
+// guard[0] = U = max_j sqrt|A_j|_F |X_j - X_0|, guard[1] = V = max_j sqrt|A_j|_F
+// over the rows with a positive weight (bits of non-negative doubles:
+// atomicMax, one per wave; zeroed by the caller; NaN counts as +inf)
+template <int D>
+__global__ __launch_bounds__(256) void local_guard_kernel(
+    const double* __restrict__ X, const double* __restrict__ w,
+    const double* __restrict__ invs, int64_t N, unsigned long long* __restrict__ guard) {
+  double U = 0.0, V = 0.0;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < N; j += (int64_t)gridDim.x * 256) {
+    if (!(w[j] > 0.0)) continue;
+    const double* A = invs + j * D * D;
+    double fa = 0.0, yy = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      const double y = X[j * D + a] - X[a];
+      yy += y * y;
+#pragma unroll
+      for (int b = 0; b < D; ++b) fa += A[a * D + b] * A[a * D + b];
+    }
+    double v = sqrt(sqrt(fa));
+    double u = v * sqrt(yy);
+    if (v != v) v = INFINITY;
+    if (u != u) u = INFINITY;
+    V = fmax(V, v);
+    U = fmax(U, u);
+  }
+  U = wave_max(U);
+  V = wave_max(V);
+  if ((threadIdx.x & 63) == 0 && U > 0.0) atomicMax(guard, (unsigned long long)__double_as_longlong(U));
+  if ((threadIdx.x & 63) == 0 && V > 0.0) atomicMax(guard + 1, (unsigned long long)__double_as_longlong(V));
+}
+
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // grid (candidate blocks of 4 waves x NT x 16, population chunks); each wave
@@ -1453,8 +1653,9 @@ template <int D>
 __global__ __launch_bounds__(256) void local_mfma_kernel(
     const double* __restrict__ x, int64_t M, const double* __restrict__ X,
     const double* __restrict__ psi, int64_t ntiles, int64_t tiles_per_chunk,
-    double2* __restrict__ part) {
+    double2* __restrict__ part, const double* __restrict__ guard) {
   constexpr int KB = LocalFeat<D>::KB, NT = LocalFeat<D>::NT;
+  if (!(guard[0] * guard[0] <= LocalFeat<D>::TMAX)) return;   // every candidate takes the direct form
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t c0 = ((int64_t)blockIdx.x * 4 + wv) * (NT * 16);
   double phi[NT][KB];
@@ -1513,7 +1714,8 @@ __global__ __launch_bounds__(256) void local_mfma_kernel(
   }
 }
 
-// sum of the weights (np.average's denominator) in a fixed order
+// sum of the weights (np.average's denominator) in a fixed order; out holds
+// 4 doubles (PdfWs::wsum)
 __global__ __launch_bounds__(1024) void local_wsum_kernel(
     const double* __restrict__ w, int64_t N, double* __restrict__ out) {
   __shared__ double sh[16];
@@ -1526,14 +1728,24 @@ __global__ __launch_bounds__(1024) void local_wsum_kernel(
     double t = 0.0;
     for (int k = 0; k < 16; ++k) t += sh[k];
     out[0] = t;
+    // the route guard's U, V and direct-form count behind it start at zero
+    out[1] = 0.0;
+    out[2] = 0.0;
+    out[3] = 0.0;
   }
 }
 
 __global__ __launch_bounds__(256) void local_combine_kernel(
     const double2* __restrict__ part, int64_t M, int nchunks,
-    const double* __restrict__ wsum, double* __restrict__ out) {
+    const double* __restrict__ wsum, double* __restrict__ out,
+    const double* __restrict__ x, const double* __restrict__ X, int d,
+    const double* __restrict__ guard, double tmax, unsigned long long* __restrict__ ndirect) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
+  // candidates the direct form answers (counted for abc_local_logpdf_route)
+  const bool direct = i < M && local_pdf_direct(x + i * d, X, d, guard, tmax);
+  const unsigned long long nd = __popcll(__ballot(direct));
+  if ((threadIdx.x & 63) == 0 && nd) atomicAdd(ndirect, nd);
+  if (i >= M || direct) return;
   double m = -INFINITY;
   for (int c = 0; c < nchunks; ++c) m = fmax(m, part[(int64_t)c * M + i].x);
   double l = 0.0;
@@ -1569,7 +1781,7 @@ struct PdfWs {
     p = PdfPlan<D>(M, N);
     psi = c.take<double>((size_t)p.ntiles * LocalFeat<D>::KB * 64);
     part = c.take<double2>((size_t)p.nch * (M > 0 ? M : 1));
-    wsum = c.take<double>(1);
+    wsum = c.take<double>(4);   // sum w | the route guard U, V | direct-form candidates
   }
 };
 
@@ -1584,20 +1796,31 @@ int launch_pdf(const double* x, int64_t M, const double* X, const double* w,
   const int64_t ntiles = plan.ntiles;
   constexpr int KB = LocalFeat<D>::KB, NT = LocalFeat<D>::NT;
   const int64_t npack = ntiles * KB * 64;
+  unsigned long long* guard = reinterpret_cast<unsigned long long*>(wsum + 1);
+  const double* uv = wsum + 1;
   hipLaunchKernelGGL(local_pack_kernel<D>, dim3((unsigned)ceil_div(npack, 256)), dim3(256), 0,
                      s, X, w, inv, lnorm, N, ntiles, psi);
   ABC_LAUNCHED();
+  // (also zeroes the guard slots: before the guard kernel)
   hipLaunchKernelGGL(local_wsum_kernel, dim3(1), dim3(1024), 0, s, w, N, wsum);
   ABC_LAUNCHED();
+  {
+    const int64_t gb = ceil_div(N, 256) < 256 ? ceil_div(N, 256) : 256;
+    hipLaunchKernelGGL(local_guard_kernel<D>, dim3((unsigned)gb), dim3(256), 0, s, X, w, inv, N,
+                       guard);
+    ABC_LAUNCHED();
+  }
   const int64_t tpc = ceil_div(ntiles, nch);
   const int64_t cblocks = ceil_div(M, 4 * NT * 16);
   hipLaunchKernelGGL(local_mfma_kernel<D>, dim3((unsigned)cblocks, (unsigned)nch), dim3(256),
-                     0, s, x, M, X, psi, ntiles, tpc, part);
+                     0, s, x, M, X, psi, ntiles, tpc, part, uv);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(local_combine_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, s,
-                     part, M, nch, wsum, out);
+                     part, M, nch, wsum, out, x, X, D, uv, LocalFeat<D>::TMAX, guard + 2);
   ABC_LAUNCHED();
-  return ABC_OK;
+  // the direct form: a block exits at once unless one of its candidates is
+  // past the bound
+  return local_wide_logpdf(x, M, X, w, N, D, inv, lnorm, out, s, uv, LocalFeat<D>::TMAX);
 }
 
 }  // namespace
@@ -1610,9 +1833,6 @@ size_t local_wide_fit_workspace(int64_t N, int d);
 int local_wide_fit(const double* X, const double* w, int64_t N, int d, int64_t nq,
                    double scaling, double eps, double* covs, double* invs, double* dets,
                    double* chol, double* lnorm, void* ws, size_t ws_bytes, hipStream_t s);
-int local_wide_logpdf(const double* x, int64_t M, const double* X, const double* w,
-                      int64_t N, int d, const double* inv, const double* lnorm,
-                      double* out, hipStream_t s);
 }  // namespace abc
 
 using namespace abc;
@@ -1635,6 +1855,7 @@ extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
   ABC_CHECK_ARG(X && w && covs && inv_covs && dets && chol && log_norm, "local_fit: null pointer");
   const int64_t nq = (k + 1) < N ? (k + 1) : N;
   hipStream_t s = as_stream(stream);
+  g_fit_route = 0;
   if (d > 16)
     return local_wide_fit(X, w, N, d, nq, scaling, eps, covs, inv_covs, dets, chol, log_norm,
                           ws, ws_bytes, s);
@@ -1646,6 +1867,8 @@ extern "C" int abc_local_fit(const double* X, const double* w, int64_t N,
     return set_error(ABC_ERR_UNSUPPORTED, "local_fit: d=%d", d);
   return rc;
 }
+
+extern "C" int abc_local_fit_route(void) { return g_fit_route; }
 
 extern "C" size_t abc_local_logpdf_workspace(int64_t M, int64_t N, int d) {
   size_t bytes = Carver::SLACK;
@@ -1671,5 +1894,32 @@ extern "C" int abc_local_logpdf(const double* x, int64_t M, const double* X,
         rc = launch_pdf<D()>(x, M, X, w, N, inv_covs, log_norm, out, ws, ws_bytes, s);
       }))
     return set_error(ABC_ERR_UNSUPPORTED, "local_logpdf: d=%d", d);
+  return rc;
+}
+
+extern "C" int abc_local_logpdf_route(int64_t M, int64_t N, int d, void* ws, size_t ws_bytes,
+                                      void* stream, int64_t* direct, double* bound) {
+  ABC_CHECK_ARG(M >= 1 && N >= 1 && d >= 1 && d <= ABC_MAX_D && direct && bound,
+                "local_logpdf_route: bad M/N/d");
+  *direct = M;
+  *bound = 0.0;
+  if (d > 16) return ABC_OK;
+  ABC_CHECK_ARG(ws, "local_logpdf_route: workspace");
+  hipStream_t s = as_stream(stream);
+  int rc = ABC_OK;
+  dispatch_int(LocalDims{}, d, [&](auto D) {
+    rc = [&]() -> int {
+      PdfWs<D()> k;
+      ABC_CARVE(k, "local_logpdf_route", M, N);
+      double g[2] = {0.0, 0.0};   // U, V
+      unsigned long long cnt = 0;
+      ABC_HIP(hipMemcpyAsync(g, k.wsum + 1, sizeof(g), hipMemcpyDeviceToHost, s));
+      ABC_HIP(hipMemcpyAsync(&cnt, k.wsum + 3, sizeof(cnt), hipMemcpyDeviceToHost, s));
+      ABC_HIP(hipStreamSynchronize(s));
+      *direct = (int64_t)cnt;
+      *bound = LOCAL_PDF_LIMIT * (g[0] * g[0] / LocalFeat<D()>::TMAX);
+      return ABC_OK;
+    }();
+  });
   return rc;
 }

@@ -402,7 +402,14 @@ constexpr int WP_ROWS = 4;   // population rows staged per LDS round
 __global__ __launch_bounds__(WT) void local_wide_pdf_kernel(
     const double* __restrict__ x, int64_t M, const double* __restrict__ X,
     const double* __restrict__ w, int64_t N, int d, const double* __restrict__ inv,
-    const double* __restrict__ lnorm, double* __restrict__ out) {
+    const double* __restrict__ lnorm, double* __restrict__ out,
+    const double* __restrict__ uv, double tmax) {
+  // d <= 16 (uv given): launched behind the MFMA route for the candidates
+  // whose cancellation bound is past tmax (abc_local.hip, LOCAL_PDF_LIMIT);
+  // a block without one exits
+  const int64_t i0 = (int64_t)blockIdx.x * WT + threadIdx.x;
+  const bool mine = !uv || (i0 < M && local_pdf_direct(x + i0 * d, X, d, uv, tmax));
+  if (!__syncthreads_or(mine)) return;
   __shared__ double sinv[WP_ROWS][WD_MAX * WD_MAX];
   __shared__ double sx[WP_ROWS][WD_MAX];
   __shared__ double sc[WP_ROWS];
@@ -451,7 +458,7 @@ __global__ __launch_bounds__(WT) void local_wide_pdf_kernel(
     if (t < o) wsum_sh[t] += wsum_sh[t + o];
     __syncthreads();
   }
-  if (i < M) out[i] = (l > 0.0) ? m + log(l) - log(wsum_sh[0]) : -INFINITY;
+  if (i < M && mine) out[i] = (l > 0.0) ? m + log(l) - log(wsum_sh[0]) : -INFINITY;
 }
 
 int wide_fit_blocks(int64_t N, int d) {
@@ -497,14 +504,14 @@ int local_wide_fit(const double* X, const double* w, int64_t N, int d, int64_t n
 
 int local_wide_logpdf(const double* x, int64_t M, const double* X, const double* w,
                       int64_t N, int d, const double* inv, const double* lnorm,
-                      double* out, hipStream_t s) {
+                      double* out, hipStream_t s, const double* uv, double tmax) {
   if (M == 0) return ABC_OK;
   if (d > WD_MAX)
     hipLaunchKernelGGL(local_wide_pdf_big_kernel, dim3((unsigned)ceil_div(M, WT)), dim3(WT), 0,
                        s, x, M, X, w, N, d, inv, lnorm, out);
   else
     hipLaunchKernelGGL(local_wide_pdf_kernel, dim3((unsigned)ceil_div(M, WT)), dim3(WT), 0, s,
-                       x, M, X, w, N, d, inv, lnorm, out);
+                       x, M, X, w, N, d, inv, lnorm, out, uv, tmax);
   ABC_LAUNCHED();
   return ABC_OK;
 }

@@ -653,6 +653,23 @@ def local_fit(X, w, k, scaling, eps):
     return covs, inv, dets, chol, lnorm
 
 
+FIT_ROUTE_NAMES = ((nat.ABC_FIT_KNN, "knn"), (nat.ABC_FIT_LIST, "list"),
+                   (nat.ABC_FIT_DENSE, "dense"), (nat.ABC_FIT_DEFER, "defer"),
+                   (nat.ABC_FIT_DENSE_REJECTED, "rejected"),
+                   (nat.ABC_FIT_SELECT_FALLBACK, "select-fallback"))
+
+
+def local_fit_route():
+    """ABC_FIT_* flags of the path the last local_fit on this thread took
+    (abc_local_fit_route: host state, no device work)."""
+    return int(nat.load().abc_local_fit_route())
+
+
+def local_fit_route_names(route=None):
+    route = local_fit_route() if route is None else route
+    return "+".join(n for f, n in FIT_ROUTE_NAMES if route & f) or "plain"
+
+
 def local_logpdf(x, X, w, inv, lnorm, out=None):
     M, d = x.shape
     N = X.shape[0]
@@ -663,6 +680,19 @@ def local_logpdf(x, X, w, inv, lnorm, out=None):
     nat.call("abc_local_logpdf", p(x), M, p(X), p(w), N, d, p(inv), p(lnorm),
              p(out), p(ws), ws.numel(), stream_ptr())
     return out
+
+
+def local_logpdf_route(M, N, d):
+    """(ndirect, bound) of the last local_logpdf with these shapes: how many
+    candidates the direct-difference form answered instead of the MFMA GEMM,
+    and the bound on the GEMM's rounding in q / 2 for a candidate at X[0]
+    (abc_local_logpdf_route; synchronises the stream)."""
+    import ctypes
+    ws = workspace(nat.query("abc_local_logpdf_workspace", M, N, d), "local_pdf")
+    direct, bound = ctypes.c_int64(0), ctypes.c_double(0.0)
+    nat.call("abc_local_logpdf_route", M, N, d, p(ws), ws.numel(), stream_ptr(),
+             ctypes.addressof(direct), ctypes.addressof(bound))
+    return int(direct.value), bound.value
 
 
 LOG_2PI = math.log(2 * math.pi)
