@@ -58,8 +58,9 @@ extern "C" {
 /* Precision of the transition-density kernel. */
 #define ABC_PREC_F64 0 /* f64 MFMA cross term: parity mode (default)   */
 #define ABC_PREC_F32 1 /* f32 MFMA cross term: fast mode (~3e-5 rel.)  */
-#define ABC_PREC_X3 2  /* f16 MFMA on 3-limb split operands: f32-grade
-                          (~1e-7 rel.), fastest; r <= 25 */
+#define ABC_PREC_X3 2  /* f16 MFMA on 3-limb split operands: 1e-6 rel.
+                          (2e-6 hinted) up to its grid cap, fastest;
+                          r <= 25 */
 
 /* Prior distribution kinds (scipy.stats names, loc/scale convention). */
 #define ABC_PRIOR_FLAT (-1)  /* no prior: density 1 everywhere (plain rvs) */
@@ -134,8 +135,9 @@ int abc_normalize_weights(double* w, int64_t N, double* stats, void* ws,
  * abc_mvn_fit's stats[3], so the fit needs no host read).  `range` (device,
  * 2 doubles, nullable; X3 only) receives max_j |y_j| in the log2-scaled
  * units of the X3 kernel (sqrt(log2 e) y) and the limb grid exponent E the
- * image was built with; the X3 image is accurate to ~1e-7 for E <= 8 (use
- * F64 otherwise).
+ * image was built with; the X3 kernel meets 1e-6 relative (2e-6 with hints)
+ * for E <= abc_mvn_x3_max_exponent() (6; 2e-7 .. 1e-6 measured at E = 6 for
+ * r = 1 .. 25) -- use F64 otherwise.
  * logpdf: out[i] = log(sum_j w_j exp(-|(x_i - X_j) U|^2 / 2)) + log_const,
  *   log_const = -(r log 2pi + log pdet)/2 - log_w_shift.  prec selects the
  *   f64-MFMA, f32-MFMA or limb-split f16-MFMA (X3) kernel.  The X3 image
@@ -187,6 +189,12 @@ size_t abc_mvn_logpdf_workspace(int64_t M, int64_t N, int r, int prec);
  * (bench.py names the instantiation its traffic file must match); no device
  * work. */
 int abc_mvn_x3_layout(int r, int* kslots, int* tiles_per_wave);
+/* Largest limb grid exponent E (the `range[1]` of abc_mvn_pack_population)
+ * the X3 kernel answers for.  An X3 image built at a larger E is marked not
+ * ok: abc_mvn_logpdf then recomputes every candidate in fp64 from the stored
+ * whitened population (correct, slow), so a caller that reads E above this
+ * value packs the population for F64 instead.  No device work. */
+int abc_mvn_x3_max_exponent(void);
 int abc_mvn_logpdf(const double* x, int64_t M, int d, const void* packed,
                    const double* X, const double* w, int64_t N,
                    const double* mu, const double* U, int r, int prec,

@@ -184,7 +184,10 @@ __global__ __launch_bounds__(256) void mvn_lse_kernel(
         for (int it = 0; it < 8; ++it) {
           if (need) {
             T mn = m[c] + (T)tmax;
-            l[c] *= exp2((double)m[c] - (double)mn);
+            // nothing accumulated yet: only m moves (a candidate more than
+            // ~38 kernel widths from the chunk's first rows lowers m by more
+            // than 1024, and 0 * exp2(that) is NaN, not 0)
+            if (l[c] > 0.0) l[c] *= exp2((double)m[c] - (double)mn);
             m[c] = mn;
           }
           V acc2 = {-m[c], -m[c], -m[c], -m[c]};

@@ -252,6 +252,12 @@ def mvn_x3_layout(r):
     return kernel, int(k.value), int(ct.value)
 
 
+def mvn_x3_max_exponent():
+    """Largest limb grid exponent E the x3 density kernel answers for (the
+    kernel's own constant): a fit whose population needs more runs f64-MFMA."""
+    return int(nat.load().abc_mvn_x3_max_exponent())
+
+
 def mvn_logpdf_direct(x, X, w, U, V, support_tol, log_const, out=None):
     M, d = x.shape
     N = X.shape[0]

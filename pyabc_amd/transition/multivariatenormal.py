@@ -75,9 +75,12 @@ class MultivariateNormalTransition(Transition):
     ``precision`` of the transition-density kernel:
 
     * "x3" (default): f16 MFMA on three-limb split operands with exact-grid
-      f32 accumulation -- f32-grade accuracy (~1e-7 relative) at the highest
-      throughput.  Populations outside its range (whitened norm beyond
-      ~200 kernel widths, rank > 25) use "f64" automatically.
+      f32 accumulation -- 1e-6 relative (2e-6 with ancestor hints; 5e-8 to
+      1e-6 measured, growing with the grid exponent and the rank) at the
+      highest throughput.  Populations outside its range (grid exponent
+      above 6: a particle beyond ~35 kernel widths of the mean at d = 10;
+      rank > 25) use "f64" automatically, ~3-4x slower; ``x3_grid()``
+      reports which.
     * "f64": f64-MFMA cross term (2e-6 relative; the exp2 is f32).
     * "f32": plain f32-MFMA cross term (~3e-5 relative at N=1e5, d=10).
     """
@@ -94,6 +97,7 @@ class MultivariateNormalTransition(Transition):
         self.cov = None
         self._normal = None
         self._fit_future = None
+        self._x3_grid = None
 
     # the KDE covariance: a host array, fetched from the device fit on use
     @property
@@ -161,6 +165,7 @@ class MultivariateNormalTransition(Transition):
             self._prec = nat.ABC_PREC_F64
         self._dev_packed = None
         self._x3_range = None
+        self._x3_grid = None
         if self._mfma and self._prec == nat.ABC_PREC_X3:
             # exponents <= 0: the shift -log max w read on the device
             packed, rng = gpu.mvn_pack(Xd, wd, self._dev_mu, U, 0.0, self._prec,
@@ -255,13 +260,14 @@ class MultivariateNormalTransition(Transition):
             self._prec = nat.ABC_PREC_F64
         self._dev_packed = None
         self._x3_range = None
+        self._x3_grid = None
         if self._mfma and self._prec == nat.ABC_PREC_X3:
             # exponents <= 0: shift by -log max w (one host read per fit)
             self._shift = -math.log(self._wmax)
             packed, rng = gpu.mvn_pack(Xd, wd, self._dev_mu, self._dev_U,
                                        self._shift, self._prec, with_range=True)
-            # range = [max whitened norm, grid exponent E]; E <= 8 keeps the
-            # dropped limb products below 2^-19 (see abc_mvn_x3.hip).  Read
+            # range = [max whitened norm, grid exponent E]; the kernel's cap
+            # on E bounds the dropped limb products (see abc_mvn_x3.hip).  Read
             # back at the first density call, not here (no host sync in fit)
             self._dev_packed = packed
             self._x3_range = gpu.HostFuture(rng)
@@ -283,9 +289,23 @@ class MultivariateNormalTransition(Transition):
             return
         self._x3_range = None
         ymax, E = rng.get()
-        if E > 8:  # population too spread for the limb grid: fp64 MFMA
+        route = "x3"
+        if E > gpu.mvn_x3_max_exponent():
+            # population too spread for the limb grid: fp64 MFMA
+            route = "f64"
             self._prec = nat.ABC_PREC_F64
             self._pack_f64()
+        self._x3_grid = (float(ymax), int(E), route)
+
+    def x3_grid(self):
+        """(max |y|, E, route) of the last fit that packed the x3 image: the
+        population's largest whitened norm in the kernel's log2-scaled units,
+        the limb grid exponent chosen from it, and the kernel that answers
+        ("x3", or "f64" above the kernel's cap).  None for a fit that never
+        packed one (other precision, singular covariance, rank > 25).  Waits
+        for the fit like the first density call does."""
+        self._check_x3_range()
+        return self._x3_grid
 
     # -- density -----------------------------------------------------------
     def logpdf_device(self, xd, out=None, hint=None):
