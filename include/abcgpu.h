@@ -408,6 +408,36 @@ int abc_pnorm_accept(const double* x, int64_t B, int S, const double* x0,
                      int max_attempts, int64_t cap, int64_t* idx, int64_t* count,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- AggregatedDistance.__call__ (pyabc/distance/distance.py:434-461) with
+ * PNormDistance children (distance.py:79-105) -------------------------------
+ * A term stack is K p-norm terms over the same row x[b, :] of x [B x S]:
+ * wf [K x S] (device; row k = child k's weights * factors in x_0 key order),
+ * p [K] (host; each >= 1 or +inf) and c [K] (host; the aggregate's weights *
+ * factors).  p and c are read on the host, before any device call, and
+ * travel in the kernel arguments.  1 <= K <= ABC_AGG_MAX_TERMS; S >= 1.
+ *   terms[b, k] (nullable, [B x K] row-major) = what abc_pnorm(x, B, S, x0,
+ *     wf + k S, p[k]) writes for row b, bit for bit;
+ *   d[b] (nullable) = ((0 + c[0] t_0) + c[1] t_1) + ..., in k order without
+ *     contraction: np.dot(weights * factors, values) in a fixed order.  Plain
+ *     IEEE: a zero weight on an infinite term is NaN, as in numpy.
+ * At least one of d and terms is given.  Up to 4 terms are evaluated per
+ * value loaded; K > 4 takes ceil(K / 4) passes whose re-reads L2 serves. */
+#define ABC_AGG_MAX_TERMS 16
+int abc_aggregate_distance(const double* x, int64_t B, int S, const double* x0,
+                           const double* wf, const double* p, const double* c, int K,
+                           double* d, double* terms, void* stream);
+/* Accept tail of one staged round for a term stack: d <= eps on
+ * abc_aggregate_distance's bits (NaN never accepted); otherwise as
+ * abc_pnorm_accept (attempts, cap, idx, count).  Replaces, for an
+ * AggregatedDistance of PNormDistances, the per-candidate accept of
+ * pyabc/model.py:163-218 via smc.py:664-724.
+ * Workspace: abc_candidates_workspace(B) bytes. */
+int abc_aggregate_accept(const double* x, int64_t B, int S, const double* x0,
+                         const double* wf, const double* p, const double* c, int K,
+                         double eps, const int32_t* attempts, int max_attempts, int64_t cap,
+                         int64_t* idx, int64_t* count, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* Gather rows: out[i, :] = in[idx[i], :] (row width `cols` doubles). */
 int abc_gather_rows(const double* in, const int64_t* idx, int64_t n, int cols,
                     double* out, void* stream);
@@ -478,6 +508,16 @@ enum { ABC_SCALE_MAD, ABC_SCALE_MEAN_AD, ABC_SCALE_STD, ABC_SCALE_BIAS, ABC_SCAL
 size_t abc_column_scale_workspace(int kind, int64_t R, int S);
 int abc_column_scale(int kind, const double* X, int64_t R, int S, const double* x0,
                      double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* AdaptiveAggregatedDistance's span scale (pyabc/distance/scale.py:138-141)
+ * of a term matrix V [R x K] (row-major, 1 <= K <= 256, R <= 2^31):
+ * out[k] = max_r V[r, k] - min_r V[r, k], exact and order-independent; a NaN
+ * anywhere in a column gives NaN.  (mean and median of a term matrix are
+ * ABC_SCALE_MEAN_AD_TO_OBS and ABC_SCALE_MAD_TO_OBS of abc_column_scale
+ * against a zero observation: terms are >= 0.)
+ * Workspace: abc_column_stats_workspace(R, K) bytes. */
+int abc_column_span(const double* V, int64_t R, int K, double* out, void* ws,
+                    size_t ws_bytes, void* stream);
 
 /* ---- LocalTransition (pyabc/transition/local_transition.py:77-145) -------
  * fit: per particle n, the k nearest other particles (ties by index),

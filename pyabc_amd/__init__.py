@@ -14,6 +14,7 @@ from .random_variables import (Distribution, RV, RVBase, RVDecorator,
 from .distance import (Distance, NoDistance, IdentityFakeDistance,
                        AcceptAllDistance, SimpleFunctionDistance,
                        PNormDistance, AdaptivePNormDistance, to_distance,
+                       AggregatedDistance, AdaptiveAggregatedDistance,
                        StochasticKernel, SimpleFunctionKernel, NormalKernel,
                        IndependentNormalKernel, IndependentLaplaceKernel,
                        BinomialKernel, PoissonKernel, NegativeBinomialKernel)

@@ -62,6 +62,10 @@ SIGNATURES = {
     "abc_candidates_round": (I32, [P, I64, I64, D, P, D, I32, I64, P, P, P, P, SZ, P]),
     "abc_candidates_regen": (I32, [P, I64, P, I64, P, P, P, P, P, P, P]),
     "abc_pnorm_accept": (I32, [P, I64, I32, P, P, D, D, P, I32, I64, P, P, P, SZ, P]),
+    "abc_aggregate_distance": (I32, [P, I64, I32, P, P, P, P, I32, P, P, P]),
+    "abc_aggregate_accept": (I32, [P, I64, I32, P, P, P, P, I32, D, P, I32, I64, P, P, P,
+                                   SZ, P]),
+    "abc_column_span": (I32, [P, I64, I32, P, P, SZ, P]),
     "abc_candidates_propose_workspace": (SZ, []),
     "abc_candidates_propose": (I32, [P, I64, I64, P, P, P, P, P, SZ, P]),
     "abc_gather_rows": (I32, [P, P, I64, I32, P, P]),
@@ -125,6 +129,7 @@ ABC_ERR_WORKSPACE = -3
 ABC_ERR_NOT_ENOUGH_PARTICLES = -4
 ABC_ERR_UNSUPPORTED = -5
 ABC_ERR_COMM = -6
+ABC_AGG_MAX_TERMS = 16
 ABC_COMM_ID_BYTES = 128
 ABC_COMM_F64, ABC_COMM_I64 = 0, 1
 ABC_COMM_SUM, ABC_COMM_MAX, ABC_COMM_MIN = 0, 1, 2

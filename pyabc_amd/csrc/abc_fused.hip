@@ -21,6 +21,7 @@
 // in full, dense across the block's waves (no lane idles behind an early
 // exit).
 #include "abc_candidate.h"
+#include "abc_aggregate.h"
 
 namespace abc {
 namespace {
@@ -645,6 +646,50 @@ __global__ __launch_bounds__(FR_T) void pnorm_accept_kernel(
   flush_accept_words(tbits, FR_WORDS, tile0, B, bits);
 }
 
+// The same tail for an AggregatedDistance of K p-norm terms
+// (distance.py:434-461; abc_aggregate.h): d of agg_row / agg_wave_rows, the
+// bits abc_aggregate_distance writes, against eps.  Accept words are per 64
+// candidates, so a block may take any multiple of 64: narrow rows one per
+// thread (AGG_TILE_ROW = FR_T rows; the K pnorm_row passes after the first
+// find the row in cache), wide rows AGG_TILE_WAVE = 64 per block, two groups
+// of PNORM_ROWS per wave -- the grid of abc_aggregate_distance's kernel
+// within a factor of two (a tile of FR_TILE rows left 196 blocks for 4e5
+// candidates on 256 CUs).
+constexpr int AGG_TILE_ROW = FR_T, AGG_TILE_WAVE = 64;
+template <bool WIDE, bool SIMPLE>
+__global__ __launch_bounds__(FR_T) void aggregate_accept_kernel(
+    const double* __restrict__ x, int64_t B, int S, const double* __restrict__ x0,
+    const double* __restrict__ wf, const AggTerms T, double eps,
+    const int32_t* __restrict__ att, int max_attempts, uint64_t* __restrict__ bits) {
+  constexpr int TILE = WIDE ? AGG_TILE_WAVE : AGG_TILE_ROW;
+  __shared__ uint32_t tbits[TILE / 32];
+  const int tid = threadIdx.x;
+  const int64_t tile0 = (int64_t)blockIdx.x * TILE;
+  if (tid < TILE / 32) tbits[tid] = 0u;
+  __syncthreads();
+  auto ok = [&](int64_t b) { return att == nullptr || att[b] <= max_attempts; };
+  if (!WIDE) {
+    const int64_t b = tile0 + tid;
+    if (b < B) {
+      const double dist = agg_row(x + b * S, S, x0, wf, T, [](int, double) {});
+      if (dist <= eps && ok(b)) atomicOr(&tbits[tid >> 5], 1u << (tid & 31));
+    }
+  } else {
+#pragma unroll 1
+    for (int r0 = (tid >> 6) * PNORM_ROWS; r0 < TILE; r0 += 4 * PNORM_ROWS) {
+      const int64_t b0 = tile0 + r0;
+      if (b0 >= B) break;  // wave-uniform
+      agg_wave_rows<SIMPLE>(x, b0, B, S, x0, wf, T, [](int, int, double) {},
+                            [&](int r, double dist) {
+        const int loc = r0 + r;
+        if (dist <= eps && ok(b0 + r)) atomicOr(&tbits[loc >> 5], 1u << (loc & 31));
+      });
+    }
+  }
+  __syncthreads();
+  flush_accept_words(tbits, TILE / 64, tile0, B, bits);
+}
+
 // *count and the positions of the first cap accepted from the range totals
 int write_ranges(const uint64_t* bits, const Ranges& rg, const int64_t* rtot, int64_t cap,
                  int64_t* idx, int64_t* count, hipStream_t s) {
@@ -896,6 +941,39 @@ extern "C" int abc_pnorm_accept(const double* x, int64_t B, int S, const double*
                        S, x0, wf, p, eps, attempts, max_attempts, bits);
   ABC_LAUNCHED();
   return compact_accept_bits(bits, w.rtot, B, cap, idx, count, s);
+}
+
+extern "C" int abc_aggregate_accept(const double* x, int64_t B, int S, const double* x0,
+                                    const double* wf, const double* p, const double* c, int K,
+                                    double eps, const int32_t* attempts, int max_attempts,
+                                    int64_t cap, int64_t* idx, int64_t* count, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  AggTerms T;
+  const int rc = agg_check_terms("aggregate_accept", S, p, c, K, T);
+  if (rc != ABC_OK) return rc;
+  ABC_CHECK_ARG(B >= 0 && cap >= 0, "aggregate_accept: bad B/cap");
+  ABC_CHECK_ARG(B < (1ll << 40), "aggregate_accept: B too large");
+  ABC_CHECK_ARG(count && (cap == 0 || idx), "aggregate_accept: null pointer");
+  RoundWs w;
+  ABC_CARVE(w, "aggregate_accept", B);
+  hipStream_t s = as_stream(stream);
+  if (B == 0) {
+    ABC_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
+    return ABC_OK;
+  }
+  ABC_CHECK_ARG(x && x0 && wf, "aggregate_accept: null pointer");
+  const int64_t nt = ceil_div(B, S <= 32 ? AGG_TILE_ROW : AGG_TILE_WAVE);
+  ABC_CHECK_ARG(nt < (1ll << 31), "aggregate_accept: too many tiles");
+  // the same row / wave split as abc_aggregate_distance (the same bits per row)
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nt), dim3(FR_T), 0, s, x, B, S, x0, wf, T, eps,
+                       attempts, max_attempts, w.bits);
+  };
+  if (S <= 32) launch(aggregate_accept_kernel<false, false>);
+  else if (agg_simple(T.p, K)) launch(aggregate_accept_kernel<true, true>);
+  else launch(aggregate_accept_kernel<true, false>);
+  ABC_LAUNCHED();
+  return compact_accept_bits(w.bits, w.rtot, B, cap, idx, count, s);
 }
 
 extern "C" int abc_prior_support_box(const int32_t* prior_kind, const double* prior_params,

@@ -357,6 +357,90 @@ def pnorm_accept(x, x0, wf, pval, eps, cap, att=None, max_attempts=0):
     return idx, cnt
 
 
+class TermStack:
+    """K p-norm terms over the same row (abc_aggregate_distance): ``wf``
+    [K, S] on the device, ``p`` and ``c`` [K] on the host (the C ABI reads
+    them there)."""
+
+    def __init__(self, wf, pvals, c):
+        pvals = np.ascontiguousarray(pvals, dtype=np.float64)
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        K = int(pvals.size)
+        if wf.dim() != 2 or wf.shape[0] != K or c.size != K:
+            raise ValueError("TermStack: wf [K, S], p [K] and c [K] disagree")
+        self.wf, self.K = wf, K
+        self.p_host, self.c_host = pvals, c      # keep the buffers alive
+
+    def args(self):
+        return (p(self.wf), self.p_host.ctypes.data, self.c_host.ctypes.data, self.K)
+
+
+def aggregate_distance(x, x0, stack, out=None, terms=False):
+    """Aggregated distance [B] of the rows of x [B, S] for a TermStack, and
+    with ``terms`` the term matrix [B, K] as well (abc_aggregate_distance)."""
+    B, S = x.shape
+    if x.dtype != F64 or not x.is_contiguous():
+        x = x.to(F64).contiguous()
+    if stack.wf.shape[1] != S:
+        raise ValueError(f"aggregate_distance: weights for {stack.wf.shape[1]} "
+                         f"statistics, rows of {S}")
+    out = torch.empty(B, dtype=F64, device=x.device) if out is None else out
+    tm = torch.empty((B, stack.K), dtype=F64, device=x.device) if terms else None
+    if B == 0:          # (empty tensors have no address to pass)
+        return (out, tm) if terms else out
+    nat.call("abc_aggregate_distance", p(x), int(B), int(S), p(x0), *stack.args(),
+             p(out), p(tm), stream_ptr())
+    return (out, tm) if terms else out
+
+
+def aggregate_accept(x, x0, stack, eps, cap, att=None, max_attempts=0):
+    """pnorm_accept for a TermStack (abc_aggregate_accept)."""
+    B, S = x.shape
+    if x.dtype != F64 or not x.is_contiguous():
+        x = x.to(F64).contiguous()
+    if stack.wf.shape[1] != S:
+        raise ValueError(f"aggregate_accept: weights for {stack.wf.shape[1]} "
+                         f"statistics, rows of {S}")
+    cap = int(min(max(cap, 0), B))
+    idx = torch.empty(max(cap, 1), dtype=I64, device=x.device)
+    cnt = torch.empty(1, dtype=I64, device=x.device)
+    nb = nat.query("abc_candidates_workspace", int(B))
+    ws = workspace(nb, "candidates")
+    nat.call("abc_aggregate_accept", p(x), int(B), int(S), p(x0), *stack.args(),
+             float(eps), p(att), int(max_attempts), cap, p(idx), p(cnt), p(ws),
+             ws.numel(), stream_ptr())
+    return idx, cnt
+
+
+class PNormTail:
+    """The staged round's accept tail for one p-norm: the round's accept
+    positions without a distance array, then the kept rows' distances."""
+
+    def __init__(self, wf, pval):
+        self.wf, self.pval = wf, pval
+
+    def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
+        return pnorm_accept(x, x0, self.wf, self.pval, eps, cap, att=att,
+                            max_attempts=max_attempts)
+
+    def distances(self, rows, x0):
+        return pnorm(rows, x0, self.wf, self.pval)
+
+
+class AggregateTail:
+    """PNormTail for a TermStack."""
+
+    def __init__(self, stack):
+        self.stack = stack
+
+    def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
+        return aggregate_accept(x, x0, self.stack, eps, cap, att=att,
+                                max_attempts=max_attempts)
+
+    def distances(self, rows, x0):
+        return aggregate_distance(rows, x0, self.stack)
+
+
 def prior_uniforms(att, k, seed, generation, idx0, B=None):
     """Uniforms in (0, 1) of the candidates' prior streams for dimension k
     (abc_prior_uniforms): the source of an ABC_PRIOR_HOST coordinate's draw."""
@@ -622,6 +706,16 @@ def column_scale(X, kind, x0=None):
     ws = workspace(nb, "colstats")
     nat.call("abc_column_scale", kind, p(X), R, S, p(x0), p(out), p(ws),
              ws.numel(), stream_ptr())
+    return out
+
+
+def column_span(V):
+    """max - min of every column of V [R, K] (abc_column_span) -> [K]."""
+    R, K = V.shape
+    out = torch.empty(K, dtype=F64, device=V.device)
+    nb = nat.query("abc_column_stats_workspace", R, K)
+    ws = workspace(nb, "colstats")
+    nat.call("abc_column_span", p(V), R, K, p(out), p(ws), ws.numel(), stream_ptr())
     return out
 
 

@@ -293,12 +293,17 @@ class BatchedGPUSampler(Sampler):
                  max_attempts=10000, check_max_eval=False, fused=True,
                  max_fused_batch_size=1 << 31, filter_below=0.0,
                  filter_min_stats=5, record_budget_bytes=1 << 31,
-                 record_device_budget_bytes=None, allow_per_candidate=True):
+                 record_device_budget_bytes=None, allow_per_candidate=True,
+                 accept_tail=True):
         super().__init__()
         # a generation without a batched form (plain closure, non-vectorised
         # model, discrete host prior, ...) runs the per-candidate loop with a
         # warning; False makes it a TypeError instead
         self.allow_per_candidate = allow_per_candidate
+        # the staged loop's one-pass accept tail (abc_pnorm_accept /
+        # abc_aggregate_accept); False: the distance array and
+        # abc_accept_compact, the same accepted rows
+        self.accept_tail = accept_tail
         self.check_max_eval = check_max_eval
         self.batch_size = batch_size
         self.max_batch_size = max_batch_size
@@ -392,9 +397,9 @@ class BatchedGPUSampler(Sampler):
         # the accept tail (abc_pnorm_accept): a p-norm distance and the
         # uniform acceptor decided in one pass over the user simulator's
         # rows, no distance array; the kept rows' distances afterwards
-        pnorm_tail = None
-        if not (stochastic or unfiltered) and hasattr(spec.distance, "fused_pnorm"):
-            pnorm_tail = spec.distance.fused_pnorm(spec.t, spec.sum_stat_keys, dev)
+        tail = None
+        if not (stochastic or unfiltered) and self.accept_tail:
+            tail = self._accept_tail(spec, dev)
         # StochasticAcceptor + record_rejected: keep every evaluated
         # candidate's (theta, density, key, ancestor) for the temperature
         rec_extra = [] if (stochastic and record) else None
@@ -413,11 +418,11 @@ class BatchedGPUSampler(Sampler):
                 host_prior_draw(theta, att, spec.host_prior, seed, gen, lo)
             x = spec.model.simulate_batch(theta, seed, gen, lo)
             dist = None
-            if pnorm_tail is not None:
+            if tail is not None:
                 if x.dtype != gpu.F64 or not x.is_contiguous():
                     x = x.to(gpu.F64).contiguous()
-                idx, cnt = gpu.pnorm_accept(x, spec.x0vec, *pnorm_tail, spec.eps,
-                                            kk, att=att, max_attempts=self.max_attempts)
+                idx, cnt = tail.accept(x, spec.x0vec, spec.eps, kk, att=att,
+                                       max_attempts=self.max_attempts)
             elif unfiltered:
                 dist = gpu.torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
                 idx = gpu.torch.arange(B, dtype=gpu.I64, device=dev)
@@ -453,8 +458,8 @@ class BatchedGPUSampler(Sampler):
             elif ws == 1:
                 # one read: the count and the index of the n-th accepted
                 # (meaningful only when this round completes the sample)
-                tail = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
-                cnt_local, pos = gpu.torch.cat([cnt.view(1), tail]).cpu().tolist()
+                nth = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
+                cnt_local, pos = gpu.torch.cat([cnt.view(1), nth]).cpu().tolist()
             else:
                 cnt_local, pos = cnt, None    # gathered on the device, one host read
             counts = dd.allgather_counts(cnt_local, dev)
@@ -464,12 +469,12 @@ class BatchedGPUSampler(Sampler):
                 lp_cols = [lp] if lp is not None else []
                 if dist is None:
                     # the tail kept no distances: the kept rows' ones, the
-                    # same per-row arithmetic (abc_pnorm)
+                    # same per-row arithmetic (abc_pnorm / abc_aggregate_distance)
                     cols = [theta] + lp_cols + [x] + ([anc] if anc is not None else [])
                     got = gpu.gather_rows_batch(cols, sel)
                     if lp is None:
                         got.insert(1, None)
-                    got.insert(2, gpu.pnorm(got[2], spec.x0vec, *pnorm_tail))
+                    got.insert(2, tail.distances(got[2], spec.x0vec))
                 else:
                     cols = [theta] + lp_cols + [dist, x] + \
                         ([anc] if anc is not None else []) + ([accw] if stochastic else [])
@@ -503,6 +508,20 @@ class BatchedGPUSampler(Sampler):
             self._acc_rate = max(int(counts.sum()) / float(ws * B), 1e-6)
         return self._finish(spec, led, kept, rec_x if record else None, rec_extra,
                             dev, d, all_accepted)
+
+    @staticmethod
+    def _accept_tail(spec, dev):
+        """The distance's one-pass accept tail for this generation (an object
+        with accept(...) and distances(rows, x0)), or None: a plain p-norm
+        (abc_pnorm_accept) or an AggregatedDistance's term stack
+        (abc_aggregate_accept)."""
+        dist = spec.distance
+        if hasattr(dist, "accept_tail"):
+            return dist.accept_tail(spec.t, spec.sum_stat_keys, dev)
+        if hasattr(dist, "fused_pnorm"):
+            fp = dist.fused_pnorm(spec.t, spec.sum_stat_keys, dev)
+            return None if fp is None else gpu.PNormTail(*fp)
+        return None
 
     def _sample_per_candidate(self, n, simulate_one, max_eval):
         """A closure the batched kernels cannot run -- a plain

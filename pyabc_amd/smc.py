@@ -104,7 +104,9 @@ class GenerationSpec:
         if self.distance is not None and (
                 not hasattr(self.distance, "device_call")
                 or not getattr(self.distance, "batched_capable", True)):
-            why.append("distance has no device kernel")
+            # (an AggregatedDistance names the child that keeps it on the host)
+            why.append(getattr(self.distance, "batched_why_not", "")
+                       or "distance has no device kernel")
         if self.transition is not None and not hasattr(self.transition,
                                                        "propose_device"):
             why.append("transition has no device kernel")
@@ -344,8 +346,9 @@ class ABCSMC:
     def _update_population_distances(self, population, t):
         """population.update_distances (population.py:147-162), batched on
         the device for columnar populations."""
-        if population.columns is not None and hasattr(self.distance_function,
-                                                      "device_call"):
+        if population.columns is not None and hasattr(
+                self.distance_function, "device_call") and not getattr(
+                self.distance_function, "batched_why_not", ""):
             x0vec = gpu.as_dev(np.array([self.x_0[k] for k in population.columns.sum_stat_keys],
                                         dtype=np.float64))
             population.update_distances_device(self.distance_function, x0vec, t)

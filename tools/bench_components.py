@@ -19,6 +19,10 @@ peak.  Inputs are synthetic, generated on the device or from seeded numpy.
   sampler   propose + simulate + pnorm + accept at the c3 batch (4.6e6)
   cv        AdaptivePopulationSize.update on the c2 population (wall time)
   e2e       whole-run generation times of c1, c4 (MAD / std), c5
+  aggregate AggregatedDistance accept tail at B = 4e5, S = 256, K = 3
+            (abc_aggregate_accept) beside the composition of single-term
+            entries that gives the same result, alternated; p in {1, 2, inf}
+            and a general-p stack
   history   History file store: a c2 population written in pyABC's schema
   stochastic StochasticAcceptor stack at the c3 batch (4.6e6 candidates):
             IndependentNormalKernel values (S = 10), tempered accept step,
@@ -434,6 +438,65 @@ def e2e(reps):
     torch.cuda.synchronize()
     emit("c5 LocalTransition fit on the run's population", "N=1e5, d=5, k=50",
          (time.perf_counter() - t0) * 1e3)
+
+
+def aggregate(reps, rounds=5):
+    """AggregatedDistance accept tail at B = 4e5, S = 256, K = 3: the one-pass
+    abc_aggregate_accept against the composition that gives the same result
+    from the single-term entries (three abc_pnorm, a torch combine,
+    abc_mask_gave_up, abc_accept_compact), alternated round by round after a
+    warm-up of each; then a general-p stack (one term p = 1.5: pow)."""
+    import torch
+    from pyabc_amd import gpu
+    rng = np.random.default_rng(99)
+    B, S, K = 400_000, 256, 3
+    x = torch.randn(B, S, dtype=torch.float64, device="cuda")
+    x0 = gpu.as_dev(rng.normal(size=S) * 0.1)
+    wf = gpu.as_dev(rng.uniform(0.5, 2.0, size=(K, S)))
+    rows = [wf[k].contiguous() for k in range(K)]
+    att = torch.ones(B, dtype=torch.int32, device="cuda")
+    c = [1.0, 0.5, 2.0]
+    cd = gpu.as_dev(np.array(c))
+    out = [torch.empty(B, dtype=torch.float64, device="cuda") for _ in range(K)]
+
+    def measure(pvals, label):
+        stack = gpu.TermStack(wf, pvals, c)
+        d = gpu.aggregate_distance(x, x0, stack)
+        eps = float(torch.quantile(d[::16], 0.1))
+
+        def one_pass():
+            return gpu.aggregate_accept(x, x0, stack, eps, B, att=att, max_attempts=10)
+
+        def composed():
+            for k in range(K):
+                gpu.pnorm(x, x0, rows[k], pvals[k], out=out[k])
+            dd = torch.zeros_like(out[0])
+            for k in range(K):
+                dd = dd + cd[k] * out[k]
+            gpu.mask_gave_up(dd, att, 10)
+            return gpu.accept_compact(dd, eps)
+
+        (i1, n1), (i2, n2) = one_pass(), composed()
+        n = int(n1.item())
+        assert n == int(n2.item()) and torch.equal(i1[:n], i2[:n])
+        t1, t2 = [], []
+        for _ in range(rounds):
+            t1.append(timed(one_pass, reps))
+            t2.append(timed(composed, reps))
+        ms1, ms2 = float(np.median(t1)), float(np.median(t2))
+        emit(f"aggregate_accept ({label})", f"B=4e5, S=256, K=3, p={pvals}", ms1,
+             bytes_=B * S * 8,
+             extra={"composed_ms": round(ms2, 4), "ratio_to_composed": round(ms1 / ms2, 3),
+                    "rounds_ms": [round(v, 4) for v in t1],
+                    "composed_rounds_ms": [round(v, 4) for v in t2], "accepted": n,
+                    "note": "includes the range-sum and position-write launches"})
+        ms = float(np.median([timed(lambda: gpu.aggregate_distance(x, x0, stack), reps)
+                              for _ in range(rounds)]))
+        emit(f"aggregate_distance ({label})", f"B=4e5, S=256, K=3, p={pvals}", ms,
+             bytes_=B * (S * 8 + 8))
+
+    measure([1.0, 2.0, float("inf")], "p in {1, 2, inf}")
+    measure([1.0, 1.5, float("inf")], "general p: pow")
 
 
 def main():
