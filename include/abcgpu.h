@@ -468,6 +468,10 @@ int abc_importance_weights(const double* prior_logpdf,
  * the knots lie in more than 2048 points of one narrow slice of the key span
  * (2^-23 of it or less; ties by the thousand) it writes NaN: the caller then runs
  * abc_weighted_quantile_sorted (full stable radix sort, always decided).
+ * The weights need not be normalised (both kernels divide by their sum).
+ * When no weight is positive, xp = 0 / 0 has no knots: both kernels write
+ * NaN, so a caller that reruns an undecided select on the sorted kernel gets
+ * NaN once more and stops there.
  * abc_weighted_quantile's workspace is zero before its first call (e.g.
  * hipMemset at allocation) and every call leaves its control block zero.
  * abc_sort_pairs_f64: stable LSD radix sort of fp64 keys carrying fp64

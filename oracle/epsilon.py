@@ -13,7 +13,7 @@ def weighted_quantile(points, weights=None, alpha=0.5, kind=None):
     weights: the reference uses numpy's default (unstable introsort) order,
     reproduced with ``kind=None``; the device radix sort is stable, i.e.
     ``kind="stable"``.  Parity at exact ties is therefore pinned to the
-    stable order only.
+    stable order only.  An array of alphas gives an array (one sort).
     """
     points = np.asarray(points, dtype=np.float64)
     order = np.argsort(points, kind=kind)
@@ -23,7 +23,8 @@ def weighted_quantile(points, weights=None, alpha=0.5, kind=None):
     else:
         w = np.asarray(weights, dtype=np.float64)[order]
     cs = np.cumsum(w)
-    return float(np.interp(alpha, cs - 0.5 * w, p))
+    q = np.interp(alpha, cs - 0.5 * w, p)
+    return float(q) if np.ndim(alpha) == 0 else q
 
 
 def quantile_epsilon(distances, weights, alpha=0.5, multiplier=1.0,

@@ -13,7 +13,7 @@
 // fixed-point integers (w * 2^(62 - ceil log2 N) / max w, truncated), so the
 // histograms' sums are exact integers, independent of any order -- the search
 // is deterministic -- and each bin's cumulative weight is known to within N
-// units.  Four kernels (the control block is left zeroed for the next
+// units.  Five kernels (the control block is left zeroed for the next
 // call, no memset); each
 // single-block step runs in the last block of the multi-block kernel before
 // it (device-scope fence + counter), so there is no one-block launch:
@@ -26,7 +26,9 @@
 //      above it) -> a key segment [lo, hi];
 //   3. hist + pick (level 2) inside that segment when it holds more than
 //      WQ_REFINE points (every block exits at once otherwise); level 1 uses
-//      2048 bins (half the global atomics), level 2 4096;
+//      2048 bins (half the global atomics), level 2 4096; a third level
+//      (4096 bins, its own launch) when level 2's segment still holds more
+//      than WQ_CAP points (half the points in 1e-4 of the range);
 //   4. gather: the segment's points (key, index, w) into a list, and the
 //      fp64 sums of the weights below the segment and of all weights (fixed
 //      per-thread order + fixed tree: deterministic); its last block sorts
@@ -38,7 +40,7 @@
 // resident grid, the points held in registers and the stages handed on by
 // counters and flags instead of kernel boundaries (wq_onepass_kernel below:
 // 0.045 vs 0.069 ms at 1e6).
-// A segment that still holds more than WQ_CAP points after level 2 (ties by
+// A segment that still holds more than WQ_CAP points after level 3 (ties by
 // the thousand at the knots, e.g. discrete distances) is not decided here:
 // *q = NaN, and the host (gpu.weighted_quantile's readers) reruns the exact
 // sort-based abc_weighted_quantile_sorted on the same inputs.
@@ -57,6 +59,7 @@ constexpr int WQ_CAP = 2048;     // list capacity (level 2's segment; ties)
 constexpr int WQ_U = 4;          // loads in flight per thread in the streaming loops
 constexpr int WQ_MAXB = 256;
 constexpr int WQ_FT = WQ_T;  // the final runs in the last gather block
+constexpr int WQ_ONE_LEVELS = 3;   // 256 (2048) x 4096 x 4096 bins over the key span at most
 static_assert(WQ_MAXB <= WQ_FT, "the final sums one gather block per thread");
 static_assert(WQ_CAP % WQ_FT == 0 && WQ_FT % WQ_REFINE == 0, "rank sort layout");
 
@@ -75,8 +78,8 @@ __device__ __forceinline__ double qval(u64 k) {
 // per-call control block, zero when a call starts (the workspace is zeroed
 // once; the gather's last block resets it): the global
 // key range (kmin stored complemented, so zero is the identity of the max
-// atomics), the last-block counters of the three multi-block stages of the
-// four-launch path, the fixed-point total and the list counter; pad != 0
+// atomics), the last-block counters of the four multi-block stages of the
+// multi-launch path, the fixed-point total and the list counter; pad != 0
 // marks a one-launch call whose wait timed out.  The one-launch path never
 // touches done[]: its arrival counters (8 group lines, one top line), its
 // hand-off flags and its range slots are the hs lines (WQ_HS_*) that follow
@@ -143,8 +146,8 @@ __global__ __launch_bounds__(WQ_T) void wq_range_kernel(const double* __restrict
                                                         unsigned int* __restrict__ ghc,
                                                         u64* __restrict__ ghw) {
   __shared__ u64 sh[WQ_T / 64];
-  // zero both levels' global histograms (the hist kernels add into them)
-  for (int64_t e = (int64_t)blockIdx.x * WQ_T + threadIdx.x; e < 2 * WQ_NB;
+  // zero every level's global histogram (the hist kernels add into them)
+  for (int64_t e = (int64_t)blockIdx.x * WQ_T + threadIdx.x; e < WQ_ONE_LEVELS * WQ_NB;
        e += (int64_t)gridDim.x * WQ_T) {
     ghc[e] = 0u;
     ghw[e] = 0ull;
@@ -455,17 +458,21 @@ __device__ void wq_pick_wave(int64_t N, double alpha, const unsigned int* ghc,
 
 // ---- 2./3. histogram of one level + its pick --------------------------------
 // level 1: the whole key range; level 2: the level-1 segment (every block
-// exits when the level-1 segment fits).  The block's LDS histogram goes into
-// the level's global histogram by integer atomics (totals independent of the
-// blocks' order); the last block picks the segment.
+// exits when the level-1 segment fits); level 3: the level-2 segment (every
+// block exits when an earlier segment fits), its result in desc[0], which
+// every block has read by the time the last block writes it.  The block's
+// LDS histogram goes into the level's global histogram by integer atomics
+// (totals independent of the blocks' order); the last block picks the
+// segment.
 template <int LEVEL>
 __global__ __launch_bounds__(WQ_T) void wq_hist_kernel(
     const double* __restrict__ x, const double* __restrict__ w, int64_t N, int64_t chunk,
     double alpha, WqCtl* __restrict__ ctl, WqDesc* __restrict__ desc,
     unsigned int* __restrict__ ghc, u64* __restrict__ ghw) {
   constexpr int BITS = LEVEL == 1 ? WQ_BITS1 : WQ_BITS, NB = 1 << BITS;
-  const WqDesc* prev = LEVEL == 2 ? desc : nullptr;
-  if (prev && prev->ok) return;
+  const WqDesc* prev = LEVEL == 1 ? nullptr : desc + (LEVEL - 2);
+  if (LEVEL >= 2 && desc[0].ok) return;
+  if (LEVEL == 3 && desc[1].ok) return;
   __shared__ unsigned int cnt[NB];
   __shared__ u64 ws[NB];
   for (int b = threadIdx.x; b < NB; b += WQ_T) { cnt[b] = 0u; ws[b] = 0ull; }
@@ -502,7 +509,7 @@ __global__ __launch_bounds__(WQ_T) void wq_hist_kernel(
   wq_pick_block<BITS>(N, alpha, ghc, ghw, lo, hi, prev ? prev->base_w : 0ull,
                       prev ? prev->below : 0, LEVEL == 1,
                       LEVEL == 1 ? 0.0 : __longlong_as_double((long long)ctl->tot), &ctl->tot,
-                      desc + (LEVEL - 1));
+                      desc + (LEVEL == 3 ? 0 : LEVEL - 1));
 }
 
 // ---- 7. final ---------------------------------------------------------------
@@ -671,7 +678,9 @@ __device__ void wq_final(const WqDesc D, int64_t N, double alpha, int nsum,
   }
   __syncthreads();
   if (t == 0) {
-    bool ok = m > 0;
+    // no positive weight at all: xp = 0 / 0 has no knots, q = NaN (the
+    // sort-based kernel answers the same, so the caller's rerun ends there)
+    bool ok = m > 0 && total > 0.0;
     double r = NAN;
     if (ok) r = interp_rules(alpha, kn[0], kn[m - 1], D.below == 0, D.below + m == N, kn, m, ok);
     *q = ok ? r : NAN;
@@ -686,7 +695,7 @@ __global__ __launch_bounds__(WQ_T) void wq_gather_final_kernel(
     u64* __restrict__ gkey, int* __restrict__ gidx, double* __restrict__ gw,
     double* __restrict__ psum, double* __restrict__ q) {
   __shared__ double sh[WQ_T / 64];
-  // the level-1 segment when it fits, else level 2's
+  // the level-1 (or level-3) segment when it fits, else level 2's
   const WqDesc D = desc[0].ok ? desc[0] : desc[1];
   {
     const int64_t b0 = (int64_t)blockIdx.x * chunk;
@@ -726,7 +735,7 @@ __global__ __launch_bounds__(WQ_T) void wq_gather_final_kernel(
       st_agent(&psum[2 * blockIdx.x + 1], all);
     }
   }
-  if (!wq_last_block(&ctl->done[2])) return;
+  if (!wq_last_block(&ctl->done[3])) return;
   wq_reset(ctl);
   __shared__ WqFinalLds L;
   wq_final(D, N, alpha, (int)gridDim.x, psum, gkey, gidx, gw, q, L);
@@ -742,7 +751,7 @@ __global__ __launch_bounds__(WQ_T) void wq_gather_final_kernel(
 // the block that brings it to the grid size runs the stage's tail alone (the
 // level's pick), publishes its result with agent-scope stores and raises a
 // flag; the others wait on the flag.  Level 1 bins on 256 bins (not 2048 as
-// the four-launch path): the flush of each block's LDS histogram into the
+// the multi-launch path): the flush of each block's LDS histogram into the
 // global one is one integer atomic per non-empty bin and block, and with
 // ~250 blocks those atomics on a few KB dominated the level (measured:
 // 28 us at 2048 bins, profiles/r06_quantile_onepass.log); level 2 then
@@ -750,11 +759,10 @@ __global__ __launch_bounds__(WQ_T) void wq_gather_final_kernel(
 // A third level (4096 bins) resolves spans whose points crowd into a tiny
 // part of the key range.
 // Deterministic (integer histograms, fixed-order fp64 sums); the segment
-// differs from the four-launch path's, so the fp64 sum below it -- and q --
+// differs from the multi-launch path's, so the fp64 sum below it -- and q --
 // may differ from that path's in the last bits (both within the 1e-12 bar).
 constexpr int64_t WQ_ONE_MAX = (int64_t)WQ_MAXB * WQ_U * WQ_T;
 constexpr int WQ_BITS1_ONE = 8;
-constexpr int WQ_ONE_LEVELS = 3;   // 256 x 4096 x 4096 bins over the key span at most
 constexpr unsigned int WQ_SPIN_MAX = 1u << 18;   // 10-300 ms of polls: a hang guard only
 
 union WqOneLds {
@@ -1069,9 +1077,9 @@ struct QuantileWs {
 extern "C" size_t abc_weighted_quantile_workspace(int64_t N) { return measure<QuantileWs>(N); }
 
 // Launches: range, level-1 histogram (its
-// last block picks), level-2 histogram (exits at once when level 1 fits; its
-// last block picks), gather (its last block sorts the list and
-// interpolates).  No single-block kernel.
+// last block picks), level-2 and level-3 histograms (each exits at once when
+// an earlier segment fits; its last block picks), gather (its last block
+// sorts the list and interpolates).  No single-block kernel.
 extern "C" int abc_weighted_quantile(const double* points, const double* w, int64_t N,
                                      double alpha, double* q, void* ws, size_t ws_bytes,
                                      void* stream) {
@@ -1097,6 +1105,9 @@ extern "C" int abc_weighted_quantile(const double* points, const double* w, int6
   ABC_LAUNCHED();
   hipLaunchKernelGGL(wq_hist_kernel<2>, dim3(nb), dim3(WQ_T), 0, s, points, w, N, chunk,
                      alpha, ctl, desc, ghc + WQ_NB, ghw + WQ_NB);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(wq_hist_kernel<3>, dim3(nb), dim3(WQ_T), 0, s, points, w, N, chunk,
+                     alpha, ctl, desc, ghc + 2 * WQ_NB, ghw + 2 * WQ_NB);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(wq_gather_final_kernel, dim3(nb), dim3(WQ_T), 0, s, points, w, N, chunk,
                      alpha, ctl, (const WqDesc*)desc, lkey, lidx, lw, psum, q);

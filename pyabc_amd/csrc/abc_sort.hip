@@ -281,6 +281,8 @@ __global__ void quantile_pick_kernel(const uint64_t* __restrict__ keys,
                                      double alpha, double* __restrict__ q) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const double total = cs[n - 1];
+  // no positive weight at all: xp = 0 / 0 has no knots (as the select)
+  if (!(total > 0.0)) { *q = NAN; return; }
   auto xp = [&](int64_t k) { return (cs[k] - 0.5 * w[k]) / total; };
   auto fp = [&](int64_t k) { return key2f(keys[k]); };
   if (alpha > xp(n - 1)) { *q = fp(n - 1); return; }
