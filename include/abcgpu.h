@@ -523,6 +523,42 @@ int abc_column_scale(int kind, const double* X, int64_t R, int S, const double* 
 int abc_column_span(const double* V, int64_t R, int K, double* out, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- the measure-list distances (pyabc/distance/distance.py:634-873) -------
+ * PCADistance.__call__ (distance.py:731-739, la.norm(W.dot(x - x_0), 2)) for
+ * B rows x [B x S]: d[b] = sqrt(sum_i (sum_j W[i, j] (x[b, j] - x0[j]))^2),
+ * W row-major [S x S] (not assumed symmetric), 1 <= S <= 256.  fp64 MFMA,
+ * fixed summation order (bitwise reproducible); plain IEEE, so a NaN or an
+ * inf in a row propagates.  B = 0 returns without a launch. */
+int abc_whitened_norm(const double* x, int64_t B, int S, const double* x0,
+                      const double* W, double* d, void* stream);
+/* Accept tail of one staged round for PCADistance: d <= eps on
+ * abc_whitened_norm's bits (NaN never accepted); otherwise as
+ * abc_pnorm_accept (attempts, cap, idx, count).  Replaces the per-candidate
+ * accept of pyabc/model.py:163-218 via smc.py:664-724.
+ * Workspace: abc_candidates_workspace(B) bytes. */
+int abc_whitened_accept(const double* x, int64_t B, int S, const double* x0,
+                        const double* W, double eps, const int32_t* attempts,
+                        int max_attempts, int64_t cap, int64_t* idx,
+                        int64_t* count, void* ws, size_t ws_bytes, void* stream);
+/* PCADistance._calculate_whitening_transformation_matrix, distance.py:709-715
+ * (means, centered, centered.T.dot(centered)) over recorded sum stats
+ * X [R x S], R >= 1, 1 <= S <= 256: mean[c] = mean_r X[r, c] and
+ * G[i, j] = sum_r (X[r, i] - mean[i]) (X[r, j] - mean[j]), row-major [S x S],
+ * two-pass, the product on fp64 MFMA over row splits combined in split
+ * order (bitwise reproducible and bitwise symmetric).
+ * Workspace: abc_column_stats_workspace(R, S) bytes. */
+int abc_column_gram(const double* X, int64_t R, int S, double* mean, double* G,
+                    void* ws, size_t ws_bytes, void* stream);
+/* PercentileDistance.upper / lower, distance.py:860-868: numpy's default
+ * ("linear") percentile 100 q per column of X [R x S], 0 <= q <= 1, R >= 1,
+ * S >= 1: with pos = q (R - 1), k = floor(pos) and
+ * g = pos - k the order statistics k and k + 1 (exact radix select)
+ * interpolated as numpy does; g = 0.5 is their mean (a + b) / 2, np.median's
+ * form and abc_column_mad's median bit for bit.  A NaN in a column gives NaN.
+ * Workspace: abc_column_stats_workspace(R, S) bytes. */
+int abc_column_quantile(const double* X, int64_t R, int S, double q, double* out,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ---- LocalTransition (pyabc/transition/local_transition.py:77-145) -------
  * fit: per particle n, the k nearest other particles (ties by index),
  * weighted covariance of their offsets (weights renormalised, unbiased

@@ -15,6 +15,8 @@ from .distance import (Distance, NoDistance, IdentityFakeDistance,
                        AcceptAllDistance, SimpleFunctionDistance,
                        PNormDistance, AdaptivePNormDistance, to_distance,
                        AggregatedDistance, AdaptiveAggregatedDistance,
+                       DistanceWithMeasureList, ZScoreDistance, PCADistance,
+                       RangeEstimatorDistance, MinMaxDistance, PercentileDistance,
                        StochasticKernel, SimpleFunctionKernel, NormalKernel,
                        IndependentNormalKernel, IndependentLaplaceKernel,
                        BinomialKernel, PoissonKernel, NegativeBinomialKernel)

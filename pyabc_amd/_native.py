@@ -66,6 +66,10 @@ SIGNATURES = {
     "abc_aggregate_accept": (I32, [P, I64, I32, P, P, P, P, I32, D, P, I32, I64, P, P, P,
                                    SZ, P]),
     "abc_column_span": (I32, [P, I64, I32, P, P, SZ, P]),
+    "abc_whitened_norm": (I32, [P, I64, I32, P, P, P, P]),
+    "abc_whitened_accept": (I32, [P, I64, I32, P, P, D, P, I32, I64, P, P, P, SZ, P]),
+    "abc_column_gram": (I32, [P, I64, I32, P, P, P, SZ, P]),
+    "abc_column_quantile": (I32, [P, I64, I32, D, P, P, SZ, P]),
     "abc_candidates_propose_workspace": (SZ, []),
     "abc_candidates_propose": (I32, [P, I64, I64, P, P, P, P, P, SZ, P]),
     "abc_gather_rows": (I32, [P, P, I64, I32, P, P]),

@@ -22,6 +22,7 @@
 // exit).
 #include "abc_candidate.h"
 #include "abc_aggregate.h"
+#include "abc_accept_words.h"
 
 namespace abc {
 namespace {
@@ -837,6 +838,20 @@ struct RoundWs {
 };
 
 extern "C" size_t abc_candidates_workspace(int64_t B) { return measure<RoundWs>(B); }
+
+// abc_accept_words.h
+bool abc::accept_words_carve(void* ws, size_t ws_bytes, int64_t B, AcceptWords& w) {
+  Carver cv(ws, ws_bytes);
+  RoundWs r;
+  r.carve(cv, B);
+  w.bits = r.bits;
+  w.rtot = r.rtot;
+  return cv.ok;
+}
+int abc::accept_words_compact(const AcceptWords& w, int64_t B, int64_t cap, int64_t* idx,
+                              int64_t* count, hipStream_t s) {
+  return compact_accept_bits(w.bits, w.rtot, B, cap, idx, count, s);
+}
 
 extern "C" int64_t abc_ancestor_table_bytes(int64_t N, int d) {
   if (N < 1 || d < 1) return 0;

@@ -34,6 +34,11 @@
 // next non-empty bin it is the minimum of that bin, taken in the next pass
 // (LDS 64-bit atomic min).  Results are exact and bitwise deterministic (the
 // selection does not depend on the order of the compacted keys).
+//
+// The rank is a parameter of the pass (RankSpec): the median's is
+// median_rank(R); abc_column_quantile (PercentileDistance,
+// distance.py:860-868) runs the same pass at numpy's percentile position,
+// the sample window centred on that rank.
 #include "abc_column_ws.h"
 
 namespace abc {
@@ -134,13 +139,40 @@ __device__ __forceinline__ uint64_t col_key(const double* __restrict__ X, int S,
 // the rank(s) the median needs: k (and k + 1 for even R)
 __host__ __device__ inline int64_t med_rank(int64_t R) { return (R & 1) ? (R - 1) / 2 : R / 2 - 1; }
 
+// What one select pass returns per column: the order statistic k, or with
+// `two` its combination with the order statistic k + 1 at weight g -- their
+// mean for g = 0.5 (np.median), else numpy's linear interpolation
+// (numpy/lib/_function_base_impl.py _lerp).  The median is the special case
+// median_rank(R).
+struct RankSpec { int64_t k; bool two; double g; };
+inline RankSpec median_rank(int64_t R) { return RankSpec{med_rank(R), (R & 1) == 0, 0.5}; }
+// np.percentile's default ("linear"): the position q (R - 1), its floor and
+// fraction.  The position is rounded as numpy rounds it
+// (_compute_virtual_index with alpha = beta = 1: n q + (1 - q) - 1), so the
+// fraction is numpy's to the last bit; exact at q = 0, 0.5 and 1.
+inline RankSpec quantile_rank(int64_t R, double q) {
+#pragma clang fp contract(off)
+  const double nq = (double)R * q, om = 1.0 - q;
+  const double pos = (nq + om) - 1.0;
+  int64_t k = (int64_t)floor(pos);
+  k = k < 0 ? 0 : (k > R - 1 ? R - 1 : k);
+  const double g = pos - (double)k;
+  const bool two = g > 0.0 && k + 1 < R;
+  return RankSpec{k, two, two ? g : 0.0};
+}
+__device__ __forceinline__ double rank_combine(double a, double b, double g) {
+  if (g == 0.5) return (a + b) / 2.0;
+  const double diff = b - a;
+  return g >= 0.5 ? b - diff * (1.0 - g) : a + diff * g;
+}
+
 // Per column: sample SMP keys, sort them and store the key window [lo, hi]
 // that brackets the wanted rank(s); columns shorter than BR_MIN get the
 // whole key range (their "window" is the column).
 template <bool DEV>
 __global__ __launch_bounds__(SEL_T) void col_sample_kernel(
     const double* __restrict__ X, int64_t R, int S, const double* __restrict__ med,
-    uint64_t* __restrict__ win, unsigned long long* __restrict__ cnt) {
+    const RankSpec rk, uint64_t* __restrict__ win, unsigned long long* __restrict__ cnt) {
   __shared__ SelShared sh;
   const int c = blockIdx.x, t = threadIdx.x;
   if (t == 0) { cnt[2 * c] = 0ull; cnt[2 * c + 1] = 0ull; }  // in window, below
@@ -154,9 +186,11 @@ __global__ __launch_bounds__(SEL_T) void col_sample_kernel(
   __syncthreads();
   sort_sample(sh);
   if (t == 0) {
-    const int64_t k = med_rank(R);
+    // the window is centred on the rank's position in the sample: BR_MARG is
+    // 5.75 sigma of the sample rank at the median and more elsewhere
+    const int64_t k = rk.k;
     const int64_t j1 = (k * SMP) / R - BR_MARG;
-    const int64_t j2 = ((k + ((R & 1) ? 0 : 1)) * SMP) / R + BR_MARG;
+    const int64_t j2 = ((k + (rk.two ? 1 : 0)) * SMP) / R + BR_MARG;
     win[2 * c] = j1 < 0 ? 0ull : sh.smp[j1];
     win[2 * c + 1] = j2 >= SMP ? ~0ull : sh.smp[j2];
   }
@@ -242,7 +276,8 @@ __global__ __launch_bounds__(BK_T) void col_bracket_kernel(
 template <bool DEV>
 __global__ __launch_bounds__(SEL_T) void col_select_kernel(
     const double* __restrict__ X, int64_t R, int S, const double* __restrict__ med,
-    const unsigned long long* __restrict__ cnt, const uint64_t* __restrict__ win,
+    const RankSpec rk, const unsigned long long* __restrict__ cnt,
+    const uint64_t* __restrict__ win,
     uint64_t* __restrict__ scratch, double* __restrict__ out) {
   __shared__ SelShared sh;
   const int c = blockIdx.x;
@@ -250,8 +285,8 @@ __global__ __launch_bounds__(SEL_T) void col_select_kernel(
   uint64_t* sc = scratch + (int64_t)c * R;
   const double m = DEV ? med[c] : 0.0;
   auto colkey = [&](int64_t i) -> uint64_t { return col_key<DEV>(X, S, c, i, m); };
-  int64_t k = med_rank(R);
-  bool want2 = (R & 1) == 0;     // still tracking rank k+1 inside the set
+  int64_t k = rk.k;
+  bool want2 = rk.two;           // still tracking rank k+1 inside the set
   bool have2 = false;            // rank k+1 resolved as a bin minimum
   uint64_t v2 = 0;
   int64_t n = R;
@@ -353,9 +388,9 @@ __global__ __launch_bounds__(SEL_T) void col_select_kernel(
   if (t == 0) {
     const double v1 = key2f_s(prefix);
     double r = v1;
-    if ((R & 1) == 0) {
+    if (rk.two) {
       const double w2 = have2 ? key2f_s(v2) : v1;  // same final bin: equal keys
-      r = (v1 + w2) / 2.0;
+      r = rank_combine(v1, w2, rk.g);
     }
     out[c] = r;
   }
@@ -363,11 +398,12 @@ __global__ __launch_bounds__(SEL_T) void col_select_kernel(
 
 }  // namespace
 
-// One select pass (sample -> bracket -> select): DEV = false
-// dst[c] = median_c(X[:, c]); DEV = true dst[c] = median_c(|X[:, c] - centre[c]|)
+// One select pass (sample -> bracket -> select) at the rank(s) rk: DEV = false
+// over X[:, c]; DEV = true over |X[:, c] - centre[c]|.  The median is
+// rk = median_rank(R).
 template <bool DEV>
 static int select_pass(const double* X, int64_t R, int S, const double* centre, double* dst,
-                       const SelectBufs& b, hipStream_t s) {
+                       const SelectBufs& b, hipStream_t s, const RankSpec rk) {
   const int CB = S < BK_T ? S : BK_T;
   const int ctiles = (int)ceil_div(S, CB);
   // expected window keys per band 2 BR_MARG / SMP = 9% x 160 x 256 = 3680 <
@@ -381,27 +417,32 @@ static int select_pass(const double* X, int64_t R, int S, const double* centre, 
   const int64_t rpb = BK_ROWS;
   const unsigned nb = (unsigned)ceil_div(R, rpb);
   hipLaunchKernelGGL(col_sample_kernel<DEV>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S, centre,
-                     b.win, b.cnt);
+                     rk, b.win, b.cnt);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(col_bracket_kernel<DEV>, dim3(nb, (unsigned)ctiles), dim3(BK_T), 0, s, X, R,
                      S, centre, (const uint64_t*)b.win, rpb, b.cnt, b.scratch);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(col_select_kernel<DEV>, dim3((unsigned)S), dim3(SEL_T), 0, s, X, R, S, centre,
-                     (const unsigned long long*)b.cnt, (const uint64_t*)b.win, b.scratch, dst);
+                     rk, (const unsigned long long*)b.cnt, (const uint64_t*)b.win, b.scratch, dst);
   ABC_LAUNCHED();
   return ABC_OK;
 }
 
 int column_mad_select(const double* X, int64_t R, int S, double* out, const SelectBufs& b,
                       hipStream_t s) {
-  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
+  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s, median_rank(R));
   if (rc) return rc;
-  return select_pass<true>(X, R, S, (const double*)b.med, out, b, s);
+  return select_pass<true>(X, R, S, (const double*)b.med, out, b, s, median_rank(R));
 }
 
 int column_absdev_median_select(const double* X, int64_t R, int S, const double* centre,
                                 double* out, const SelectBufs& b, hipStream_t s) {
-  return select_pass<true>(X, R, S, centre, out, b, s);
+  return select_pass<true>(X, R, S, centre, out, b, s, median_rank(R));
+}
+
+int column_quantile_select(const double* X, int64_t R, int S, double q, double* out,
+                           const SelectBufs& b, hipStream_t s) {
+  return select_pass<false>(X, R, S, (const double*)b.med, out, b, s, quantile_rank(R, q));
 }
 
 namespace {
@@ -415,11 +456,11 @@ int column_cmad_select(const double* X, int64_t R, int S, const double* x0, doub
                        const CmadBufs& w, hipStream_t s) {
   const SelectBufs& b = w.sel;
   double* mad = w.mad;
-  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s);
+  int rc = select_pass<false>(X, R, S, (const double*)b.med, b.med, b, s, median_rank(R));
   if (rc) return rc;
-  rc = select_pass<true>(X, R, S, (const double*)b.med, mad, b, s);
+  rc = select_pass<true>(X, R, S, (const double*)b.med, mad, b, s, median_rank(R));
   if (rc) return rc;
-  rc = select_pass<true>(X, R, S, x0, out, b, s);
+  rc = select_pass<true>(X, R, S, x0, out, b, s, median_rank(R));
   if (rc) return rc;
   hipLaunchKernelGGL(add_columns_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s,
                      (const double*)mad, S, out);

@@ -349,13 +349,20 @@ __global__ void colsum_final(const double* __restrict__ part, int nblk, int S,
 
 }  // namespace
 
-int column_std(const double* X, int64_t R, int S, double* out, const ColumnStdBufs& b,
-               hipStream_t s) {
+int column_mean(const double* X, int64_t R, int S, const ColumnStdBufs& b, hipStream_t s) {
   const int nblk = (int)(R < CS_BLOCKS ? R : CS_BLOCKS);
   hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)nullptr, b.part);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, b.part, nblk, S, R, b.mean, false);
   ABC_LAUNCHED();
+  return ABC_OK;
+}
+
+int column_std(const double* X, int64_t R, int S, double* out, const ColumnStdBufs& b,
+               hipStream_t s) {
+  const int nblk = (int)(R < CS_BLOCKS ? R : CS_BLOCKS);
+  const int rc = column_mean(X, R, S, b, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(colsum_kernel, dim3(nblk), dim3(256), 0, s, X, R, S, (const double*)b.mean, b.part);
   ABC_LAUNCHED();
   hipLaunchKernelGGL(colsum_final, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, b.part, nblk, S, R, out, true);

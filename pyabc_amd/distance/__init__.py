@@ -3,6 +3,9 @@ from .base import (Distance, NoDistance, IdentityFakeDistance,
                    AcceptAllDistance, SimpleFunctionDistance, to_distance)
 from .distance import PNormDistance, AdaptivePNormDistance, SumStatMatrix
 from .aggregate import AggregatedDistance, AdaptiveAggregatedDistance
+from .measure_list import (DistanceWithMeasureList, ZScoreDistance, PCADistance,
+                           RangeEstimatorDistance, MinMaxDistance,
+                           PercentileDistance)
 from .scale import (median_absolute_deviation, mean_absolute_deviation,
                     standard_deviation, bias, root_mean_square_deviation,
                     median_absolute_deviation_to_observation,

@@ -441,6 +441,54 @@ class AggregateTail:
         return aggregate_distance(rows, x0, self.stack)
 
 
+def _whiten_check(x, W):
+    B, S = x.shape
+    if W.dim() != 2 or W.shape[0] != S or W.shape[1] != S:
+        raise ValueError(f"whitened norm: W {tuple(W.shape)} for rows of {S}")
+    if x.dtype != F64 or not x.is_contiguous():
+        x = x.to(F64).contiguous()
+    return x, int(B), int(S)
+
+
+def whitened_norm(x, x0, W, out=None):
+    """|W (x_b - x0)|_2 of the rows of x [B, S] for a device matrix W [S, S]
+    (abc_whitened_norm) -> [B]."""
+    x, B, S = _whiten_check(x, W)
+    out = torch.empty(B, dtype=F64, device=x.device) if out is None else out
+    if B == 0:          # (empty tensors have no address to pass)
+        return out
+    nat.call("abc_whitened_norm", p(x), B, S, p(x0), p(W), p(out), stream_ptr())
+    return out
+
+
+def whitened_accept(x, x0, W, eps, cap, att=None, max_attempts=0):
+    """pnorm_accept for the whitened norm (abc_whitened_accept)."""
+    x, B, S = _whiten_check(x, W)
+    cap = int(min(max(cap, 0), B))
+    idx = torch.empty(max(cap, 1), dtype=I64, device=x.device)
+    cnt = torch.empty(1, dtype=I64, device=x.device)
+    nb = nat.query("abc_candidates_workspace", B)
+    ws = workspace(nb, "candidates")
+    nat.call("abc_whitened_accept", p(x) if B else None, B, S, p(x0), p(W), float(eps),
+             p(att), int(max_attempts), cap, p(idx), p(cnt), p(ws), ws.numel(),
+             stream_ptr())
+    return idx, cnt
+
+
+class WhitenedTail:
+    """PNormTail for the whitened norm of a device matrix W [S, S]."""
+
+    def __init__(self, W):
+        self.W = W
+
+    def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
+        return whitened_accept(x, x0, self.W, eps, cap, att=att,
+                               max_attempts=max_attempts)
+
+    def distances(self, rows, x0):
+        return whitened_norm(rows, x0, self.W)
+
+
 def prior_uniforms(att, k, seed, generation, idx0, B=None):
     """Uniforms in (0, 1) of the candidates' prior streams for dimension k
     (abc_prior_uniforms): the source of an ABC_PRIOR_HOST coordinate's draw."""
@@ -716,6 +764,31 @@ def column_span(V):
     nb = nat.query("abc_column_stats_workspace", R, K)
     ws = workspace(nb, "colstats")
     nat.call("abc_column_span", p(V), R, K, p(out), p(ws), ws.numel(), stream_ptr())
+    return out
+
+
+def column_gram(X):
+    """Column means [S] and the centred Gram matrix [S, S] of X [R, S]
+    (abc_column_gram)."""
+    R, S = X.shape
+    mean = torch.empty(S, dtype=F64, device=X.device)
+    G = torch.empty((S, S), dtype=F64, device=X.device)
+    nb = nat.query("abc_column_stats_workspace", R, S)
+    ws = workspace(nb, "colstats")
+    nat.call("abc_column_gram", p(X), R, S, p(mean), p(G), p(ws), ws.numel(),
+             stream_ptr())
+    return mean, G
+
+
+def column_quantile(X, q):
+    """numpy's default percentile 100 q of every column of X [R, S]
+    (abc_column_quantile) -> [S]."""
+    R, S = X.shape
+    out = torch.empty(S, dtype=F64, device=X.device)
+    nb = nat.query("abc_column_stats_workspace", R, S)
+    ws = workspace(nb, "colstats")
+    nat.call("abc_column_quantile", p(X), R, S, float(q), p(out), p(ws), ws.numel(),
+             stream_ptr())
     return out
 
 

@@ -23,6 +23,11 @@ peak.  Inputs are synthetic, generated on the device or from seeded numpy.
             (abc_aggregate_accept) beside the composition of single-term
             entries that gives the same result, alternated; p in {1, 2, inf}
             and a general-p stack
+  whiten    PCADistance accept tail (abc_whitened_accept) at B = 4e5 with
+            S = 10 and S = 256 beside abc_pnorm_accept at the same shape (the
+            same bytes: the memory floor) and its own roofline, alternated;
+            abc_column_gram and abc_column_quantile on the c4 matrix beside
+            abc_column_std and abc_column_mad
   history   History file store: a c2 population written in pyABC's schema
   stochastic StochasticAcceptor stack at the c3 batch (4.6e6 candidates):
             IndependentNormalKernel values (S = 10), tempered accept step,
@@ -497,6 +502,85 @@ def aggregate(reps, rounds=5):
 
     measure([1.0, 2.0, float("inf")], "p in {1, 2, inf}")
     measure([1.0, 1.5, float("inf")], "general p: pow")
+
+
+F64_MFMA_PEAK = 78.6e12    # FLOP/s fp64 matrix (spec)
+
+
+def whiten(reps, rounds=5):
+    """abc_whitened_accept at B = 4e5, S in {10, 256} against abc_pnorm_accept
+    on the same rows (the same bytes) and the roofline max(8 B S / HBM,
+    2 B S^2 / fp64 MFMA peak), alternated round by round; then the Gram
+    matrix and two percentiles of the c4 matrix beside its std and MAD."""
+    import torch
+    from pyabc_amd import gpu
+    rng = np.random.default_rng(7)
+    B = 400_000
+    for S in (10, 256):
+        x = torch.randn(B, S, dtype=torch.float64, device="cuda")
+        x0 = gpu.as_dev(rng.normal(size=S) * 0.1)
+        W = gpu.as_dev(rng.normal(size=(S, S)) / np.sqrt(S))
+        wf = gpu.as_dev(rng.uniform(0.5, 2.0, size=S))
+        att = torch.ones(B, dtype=torch.int32, device="cuda")
+        d = gpu.whitened_norm(x, x0, W)
+        eps = float(torch.quantile(d[::16], 0.1))
+        d2 = gpu.pnorm(x, x0, wf, 2.0)
+        eps2 = float(torch.quantile(d2[::16], 0.1))
+
+        def tail():
+            return gpu.whitened_accept(x, x0, W, eps, B, att=att, max_attempts=10)
+
+        def floor():
+            return gpu.pnorm_accept(x, x0, wf, 2.0, eps2, B, att=att, max_attempts=10)
+
+        (i1, n1), (i2, n2) = tail(), gpu.accept_compact(d, eps)
+        n = int(n1.item())
+        assert n == int(n2.item()) and torch.equal(i1[:n], i2[:n])
+        t1, t2, t3 = [], [], []
+        for _ in range(rounds):
+            t1.append(timed(tail, reps))
+            t2.append(timed(floor, reps))
+            t3.append(timed(lambda: gpu.whitened_norm(x, x0, W, out=d), reps))
+        ms1, ms2, ms3 = (float(np.median(t)) for t in (t1, t2, t3))
+        roof_ms = max(8.0 * B * S / HBM_PEAK, 2.0 * B * S * S / F64_MFMA_PEAK) * 1e3
+        emit("whitened_accept (PCADistance tail)", f"B=4e5, S={S}", ms1, bytes_=B * S * 8,
+             extra={"algorithmic_flop": 2 * B * S * S,
+                    "achieved_TFLOPs": round(2 * B * S * S / (ms1 * 1e-3) / 1e12, 3),
+                    "roofline_ms": round(roof_ms, 4), "ratio_to_roofline": round(ms1 / roof_ms, 2),
+                    "pnorm_accept_ms": round(ms2, 4), "ratio_to_pnorm_accept": round(ms1 / ms2, 2),
+                    "whitened_norm_ms": round(ms3, 4),
+                    "rounds_ms": [round(v, 4) for v in t1],
+                    "pnorm_accept_rounds_ms": [round(v, 4) for v in t2], "accepted": n,
+                    "note": "includes the range-sum and position-write launches"})
+    # the c4 recorded matrix (c4()'s construction)
+    S, R = 256, 670_000
+    a = rng.uniform(0.5, 2.0, S)
+    sig = 10.0 ** rng.uniform(-2, 2, S)
+    theta = torch.randn(R, 4, dtype=torch.float64, device="cuda")
+    src = torch.as_tensor(np.arange(S) % 4, device="cuda")
+    X = (theta[:, src] * torch.as_tensor(a, device="cuda") +
+         torch.randn(R, S, dtype=torch.float64, device="cuda") *
+         torch.as_tensor(sig, device="cuda")).contiguous()
+    fns = {"column std": lambda: gpu.column_std(X), "column MAD": lambda: gpu.column_mad(X),
+           "column gram": lambda: gpu.column_gram(X),
+           "column quantile (q = 0.2)": lambda: gpu.column_quantile(X, 0.2),
+           "column quantile (q = 0.8)": lambda: gpu.column_quantile(X, 0.8)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, max(1, reps // 2)))
+    for k, ts in times.items():
+        passes = {"column std": 2, "column MAD": 2, "column gram": 2}.get(k, 2)
+        emit(k, "c4: [6.7e5 x 256] recorded", float(np.median(ts)),
+             bytes_=R * S * 8 * passes,
+             extra={"rounds_ms": [round(v, 4) for v in ts],
+                    **({"algorithmic_flop": 2 * R * S * S,
+                        "achieved_TFLOPs": round(2 * R * S * S / (np.median(ts) * 1e-3) / 1e12, 3)}
+                       if k == "column gram" else {}),
+                    "note": {"column gram": "mean pass + centred product",
+                             "column std": "two-pass: mean, then squares",
+                             "column MAD": "median pass + deviation pass"}.get(
+                                 k, "NaN scan + one select pass")})
 
 
 def main():
