@@ -111,15 +111,34 @@ int abc_weighted_moments(const double* X, const double* w, int64_t N, int d,
 
 /* Inclusive prefix sum (fp64), the cumulative weights behind
  * np.random.choice(p=w) in MultivariateNormalTransition.rvs
- * (multivariatenormal.py:85-91). */
+ * (multivariatenormal.py:85-91).  For in[i] >= 0 the output is a cdf by
+ * construction, not by luck of the rounding:
+ *   out[i] >= out[i-1];  out[i] == out[i-1] where in[i] == 0;  out[0] == in[0];
+ *   |out[i] - exact[i]| <= m u exact[i] / (1 - m u),  u = 2^-53,
+ *   m = 8 + 256 + ceil(N / 2048) roundings at most on any term
+ * (three levels of left-to-right chains; the next thread's and the next
+ * tile's offset is the very value the previous one ended on -- DESIGN.md,
+ * "The weight chain").  The ancestor searches assume exactly this.  A
+ * positive in[i] far below out[i-1] may be absorbed (out[i] == out[i-1]).
+ * Bitwise reproducible.  Negative or NaN input: no guarantee. */
 size_t abc_scan_workspace(int64_t N);
 int abc_inclusive_scan_f64(const double* in, double* out, int64_t N, void* ws,
                            size_t ws_bytes, void* stream);
 
 /* Population._normalize_weights (pyabc/population.py:123-145, one model) and
  * effective_sample_size (pyabc/weighted_statistics.py:73-83): w /= sum w in
- * place; stats[0] = sum w (before), stats[1] = ESS = (sum w)^2 / sum w^2,
- * stats[2] = sum w^2 (before). */
+ * place; stats[0] = sum w (before), stats[1] = ESS, stats[2] = sum w^2
+ * (before).
+ * The ESS is 1 / sum w_n^2 over the NORMALISED weights w_n = w / sum w, as
+ * the reference takes it, so it does not depend on the scale of the raw
+ * weights: w and 2^k w give the same w_n and the same ESS, bit for bit, as
+ * long as sum w neither overflows nor leaves the normal range.  stats[2] is
+ * the raw sum of squares, which underflows for weights below ~1e-154 and
+ * overflows above ~1e154: it is reported as it comes and nothing derives the
+ * ESS (or anything else) from it.
+ * N = 1: w = 1.0 and ESS = 1.0 exactly.  All weights zero: stats[0] = 0,
+ * stats[2] = 0, every w and the ESS are NaN (0 / 0) -- the caller decides;
+ * no error is raised on the device. */
 size_t abc_normalize_weights_workspace(int64_t N);
 int abc_normalize_weights(double* w, int64_t N, double* stats, void* ws,
                           size_t ws_bytes, void* stream);
@@ -454,7 +473,12 @@ int abc_gather_rows_batch(int n_arrays, const double* const* ins,
 /* ---- importance weight (smc.py:768-811, single model) --------------------
  * w[i] = exp(prior_logpdf[i] - trans_logpdf[i]) * scale * acc_weights[i]
  * (t > 0; acc_weights = the StochasticAcceptor's acceptance weights, NULL
- * for the uniform acceptor). */
+ * for the uniform acceptor).  Evaluated left to right in fp64: the
+ * difference is rounded before exp, so the relative error is
+ * |lp - lt| 2^-53 + (exp's 1 ulp) + 1/2 ulp per multiply; results in the
+ * subnormal range are good to a few subnormal spacings instead.
+ * prior_logpdf = -inf gives exactly 0, trans_logpdf = -inf gives +inf (for a
+ * positive scale), NaN in any input gives NaN. */
 int abc_importance_weights(const double* prior_logpdf,
                            const double* trans_logpdf,
                            const double* acc_weights, int64_t A, double scale,

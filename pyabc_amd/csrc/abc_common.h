@@ -260,9 +260,12 @@ __device__ __forceinline__ bool local_pdf_direct(const double* xi, const double*
 
 // ---- block helpers -----------------------------------------------------------
 // Exclusive scan of one value per thread over a block of NT threads:
-// Hillis-Steele in LDS (sh[NT]), fixed order, so deterministic for doubles
-// too.  total receives the block's sum.  Every thread of the block calls it
-// (barriers inside); sh may be reused once it returns.
+// Hillis-Steele in LDS (sh[NT]), fixed order.  For integer T only: the
+// exclusive value is the inclusive one minus v, which is exact for integers
+// and is neither exact nor monotone for floating point (the fp64 cdf scan of
+// abc_reduce.hip has its own chains).  total receives the block's sum.  Every
+// thread of the block calls it (barriers inside); sh may be reused once it
+// returns.
 template <class T, int NT>
 __device__ __forceinline__ T block_exscan(T v, T* sh, T& total) {
   const int t = threadIdx.x;

@@ -302,37 +302,82 @@ void moments_fast(const double* X, const double* w, int64_t N, double* out,
 }
 
 // ---- scan -------------------------------------------------------------------
+// out[i] = fl(O_b + fl(P_t + L_k)) for item k of thread t of tile b, three
+// levels of left-to-right chains, each started from 0:
+//   L_k      = the thread's items 0..k added in order         (<= SCAN_I terms)
+//   P_{t+1}  = fl(P_t + L_last of thread t), P_0 = 0          (<= SCAN_T terms)
+//   O_{b+1}  = fl(O_b + P_SCAN_T of tile b), O_0 = 0          (ntile terms)
+// The offset of the next thread (tile) IS the value the previous thread's
+// (tile's) last item is built from -- no tree sum stands next to a
+// sequential one, and nothing is obtained by subtraction.  With weights >= 0
+// and rounding monotone this gives, by construction:
+//   nondecreasing   L_k is, so fl(P_t + L_k) and fl(O_b + .) are; the last
+//                   item of thread t is fl(O_b + P_{t+1}), the first of
+//                   thread t + 1 is fl(O_b + fl(P_{t+1} + v)) >= that; the
+//                   last item of tile b is O_{b+1}, the first of tile b + 1 is
+//                   fl(O_{b+1} + v) >= that;
+//   flat on zeros   v = 0 turns each of those >= into ==; out[0] == in[0];
+//   accuracy        every out[i] is a sum of non-negative terms in which no
+//                   term meets more than SCAN_I + SCAN_T + ntile roundings.
+// The chains are serial (one thread walks the block's SCAN_T thread sums, one
+// thread the ntile tile sums): N / 2048 + 256 dependent adds per scan, which
+// a scan that runs once per generation does not notice.  Fixed order, so
+// bitwise reproducible.
 constexpr int SCAN_T = 256, SCAN_I = 8, SCAN_TILE = SCAN_T * SCAN_I;
+
+// this thread's items added in order -> sh[t]; thread 0 turns sh into the
+// exclusive chain P_t in place and returns P_SCAN_T through sh_tot.  Every
+// thread of the block calls it.
+__device__ __forceinline__ void scan_thread_chain(double s, double* sh, double* sh_tot) {
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double run = 0.0;
+    for (int t = 0; t < SCAN_T; ++t) {
+      const double v = sh[t];
+      sh[t] = run;
+      run += v;
+    }
+    *sh_tot = run;
+  }
+  __syncthreads();
+}
 
 __global__ __launch_bounds__(SCAN_T) void scan_tile_sums(
     const double* __restrict__ in, int64_t N, double* __restrict__ sums) {
   __shared__ double sh[SCAN_T];
+  __shared__ double tot;
   const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_I;
   double s = 0.0;
   for (int k = 0; k < SCAN_I; ++k)
     if (base + k < N) s += in[base + k];
-  double tot;
-  block_exscan<double, SCAN_T>(s, sh, tot);
+  scan_thread_chain(s, sh, &tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
+// tile sums -> the exclusive chain O_b, in place: one block stages SCAN_T
+// sums at a time in LDS, thread 0 walks them, carrying O across the stages
 __global__ __launch_bounds__(SCAN_T) void scan_sums(double* __restrict__ sums,
                                                     int64_t n) {
-  // exclusive scan of n tile sums, sequential chunks per thread
   __shared__ double sh[SCAN_T];
-  const int64_t per = (n + SCAN_T - 1) / SCAN_T;
-  const int64_t b0 = threadIdx.x * per;
-  double s = 0.0;
-  for (int64_t k = 0; k < per; ++k)
-    if (b0 + k < n) s += sums[b0 + k];
-  double tot;
-  double off = block_exscan<double, SCAN_T>(s, sh, tot);
-  for (int64_t k = 0; k < per; ++k) {
-    if (b0 + k < n) {
-      double v = sums[b0 + k];
-      sums[b0 + k] = off;
-      off += v;
+  __shared__ double carry;
+  if (threadIdx.x == 0) carry = 0.0;
+  for (int64_t b0 = 0; b0 < n; b0 += SCAN_T) {
+    const int64_t b = b0 + threadIdx.x;
+    sh[threadIdx.x] = b < n ? sums[b] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double run = carry;
+      for (int t = 0; t < SCAN_T; ++t) {
+        const double v = sh[t];
+        sh[t] = run;
+        run += v;
+      }
+      carry = run;
     }
+    __syncthreads();
+    if (b < n) sums[b] = sh[threadIdx.x];
+    __syncthreads();
   }
 }
 
@@ -340,6 +385,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_apply(
     const double* __restrict__ in, int64_t N, const double* __restrict__ sums,
     double* __restrict__ out) {
   __shared__ double sh[SCAN_T];
+  __shared__ double tot;
   const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_I;
   double v[SCAN_I];
   double s = 0.0;
@@ -347,11 +393,12 @@ __global__ __launch_bounds__(SCAN_T) void scan_apply(
     v[k] = (base + k < N) ? in[base + k] : 0.0;
     s += v[k];
   }
-  double tot;
-  double run = block_exscan<double, SCAN_T>(s, sh, tot) + sums[blockIdx.x];
+  scan_thread_chain(s, sh, &tot);   // the same adds as scan_tile_sums
+  const double pt = sh[threadIdx.x], ob = sums[blockIdx.x];
+  double run = 0.0;
   for (int k = 0; k < SCAN_I; ++k) {
     run += v[k];
-    if (base + k < N) out[base + k] = run;
+    if (base + k < N) out[base + k] = ob + (pt + run);
   }
 }
 
@@ -396,8 +443,21 @@ __global__ void importance_weights_kernel(const double* __restrict__ lp,
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < A) {
     // prior_pd * acceptance_weight * fraction / transition_pd (smc.py:803-809)
-    double v = exp(lp[i] - lt[i]) * scale;
-    w[i] = accw ? v * accw[i] : v;
+    // Past |lp - lt| = 700 exp alone overflows (709.78) or goes subnormal
+    // (-708.4) where exp * scale need not: 0.3 e^710 is a finite double.
+    // There exp(x) is taken as exp(x / 2)^2 around the other factors (x / 2
+    // is exact; one multiply more), so that only the last product can leave
+    // the normal range.  NaN takes this branch and stays NaN.
+    const double x = lp[i] - lt[i];
+    if (fabs(x) <= 700.0) {
+      const double v = exp(x) * scale;
+      w[i] = accw ? v * accw[i] : v;
+    } else {
+      const double h = exp(0.5 * x);
+      double v = h * scale;
+      if (accw) v *= accw[i];
+      w[i] = v * h;
+    }
   }
 }
 
@@ -422,19 +482,59 @@ __global__ __launch_bounds__(256) void wsum_kernel(const double* __restrict__ w,
     part[2 * blockIdx.x + 1] = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
   }
 }
-__global__ void wsum_final(const double* __restrict__ part, int nblk,
-                           double* __restrict__ stats) {
-  if (threadIdx.x != 0) return;
+// The finals add the NW_BLOCKS partials in block order, one thread, as a
+// fixed-length chain (absent blocks count 0.0, which changes no sum): the
+// partials are staged in LDS by the whole block first, so the chain waits on
+// no global load.
+__global__ __launch_bounds__(NW_BLOCKS) void wsum_final(const double* __restrict__ part,
+                                                        int nblk,
+                                                        double* __restrict__ stats) {
+  __shared__ double sh[2][NW_BLOCKS];
+  const int b = threadIdx.x;
+  sh[0][b] = b < nblk ? part[2 * b] : 0.0;
+  sh[1][b] = b < nblk ? part[2 * b + 1] : 0.0;
+  __syncthreads();
+  if (b != 0) return;
   double s = 0.0, s2 = 0.0;
-  for (int b = 0; b < nblk; ++b) { s += part[2 * b]; s2 += part[2 * b + 1]; }
+  for (int k = 0; k < NW_BLOCKS; ++k) { s += sh[0][k]; s2 += sh[1][k]; }
   stats[0] = s;             // sum w
-  stats[1] = s * s / s2;    // ESS (weighted_statistics.py:73-83)
-  stats[2] = s2;
+  stats[2] = s2;            // sum w^2 of the raw weights: reported, never used
 }
-__global__ void wscale_kernel(double* __restrict__ w, int64_t N,
-                              const double* __restrict__ stats) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) w[i] = w[i] / stats[0];
+// w /= sum w, and the block's sum of the squared NORMALISED weights (same
+// grid and combine order as wsum_kernel).  The ESS is taken from these: the
+// raw weights exp(lp - lt) * scale reach 1e-170 and below with a tight kernel
+// in many dimensions, where their squares are subnormal or 0, while a
+// normalised weight is <= 1 and the sum of their squares is >= 1 / N.
+__global__ __launch_bounds__(256) void wscale_kernel(double* __restrict__ w, int64_t N,
+                                                     const double* __restrict__ stats,
+                                                     double* __restrict__ part) {
+  const double sw = stats[0];
+  double s2 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N;
+       i += (int64_t)gridDim.x * 256) {
+    const double v = w[i] / sw;
+    w[i] = v;
+    s2 += v * v;
+  }
+  __shared__ double sh[4];
+  s2 = wave_sum(s2);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s2;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+// ESS = 1 / sum w_n^2 (weighted_statistics.py:73-83 on weights that sum to 1:
+// the reference normalises before it takes the ESS)
+__global__ __launch_bounds__(NW_BLOCKS) void wess_final(const double* __restrict__ part,
+                                                        int nblk,
+                                                        double* __restrict__ stats) {
+  __shared__ double sh[NW_BLOCKS];
+  const int b = threadIdx.x;
+  sh[b] = b < nblk ? part[b] : 0.0;
+  __syncthreads();
+  if (b != 0) return;
+  double s2 = 0.0;
+  for (int k = 0; k < NW_BLOCKS; ++k) s2 += sh[k];
+  stats[1] = 1.0 / s2;
 }
 
 }  // namespace
@@ -604,9 +704,12 @@ extern "C" int abc_normalize_weights(double* w, int64_t N, double* stats,
   double* part = k.part;
   hipLaunchKernelGGL(wsum_kernel, dim3(nblk), dim3(256), 0, s, w, N, part);
   ABC_LAUNCHED();
-  hipLaunchKernelGGL(wsum_final, dim3(1), dim3(64), 0, s, part, nblk, stats);
+  hipLaunchKernelGGL(wsum_final, dim3(1), dim3(NW_BLOCKS), 0, s, part, nblk, stats);
   ABC_LAUNCHED();
-  hipLaunchKernelGGL(wscale_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, w, N, stats);
+  // part is free again once wsum_final has read it
+  hipLaunchKernelGGL(wscale_kernel, dim3(nblk), dim3(256), 0, s, w, N, stats, part);
+  ABC_LAUNCHED();
+  hipLaunchKernelGGL(wess_final, dim3(1), dim3(NW_BLOCKS), 0, s, part, nblk, stats);
   ABC_LAUNCHED();
   return ABC_OK;
 }

@@ -14,6 +14,8 @@ peak.  Inputs are synthetic, generated on the device or from seeded numpy.
             every abc_column_scale kind on that matrix, alternated with
             column_std and column_mad round by round (ratio to them)
   quantile  QuantileEpsilon weighted quantile at N = 1e6 (c3) and 1e5 (c2)
+  weights   importance weights, normalisation + ESS and the cdf scan at
+            N = 1e6 (c3) and 1e5 (c2)
   c5        LocalTransition d = 5, N = 1e5: k-NN covariance fit (k = 50 and
             the default k = N/4 = 25000), density of 1e5 candidates
   sampler   propose + simulate + pnorm + accept at the c3 batch (4.6e6)
@@ -157,6 +159,26 @@ def quantile(reps):
         ms = timed(lambda: gpu.weighted_quantile(d, w, 0.5), reps)
         emit("weighted quantile (QuantileEpsilon)", f"{tag}: N={N}", ms,
              bytes_=N * 16)
+
+
+def weights(reps):
+    """The per-generation weight chain at the c3 and c2 populations:
+    importance weights, normalisation + ESS, the cdf scan (each runs once per
+    generation over the accepted population)."""
+    import torch
+    from pyabc_amd import gpu
+    for N, tag in ((1_000_000, "c3"), (100_000, "c2")):
+        lp = torch.randn(N, dtype=torch.float64, device="cuda")
+        lt = torch.randn(N, dtype=torch.float64, device="cuda") * 3
+        w = torch.rand(N, dtype=torch.float64, device="cuda")
+        out = torch.empty_like(w)
+        ms = timed(lambda: gpu.importance_weights(lp, lt, 0.3), reps)
+        emit("importance weights", f"{tag}: N={N}", ms, bytes_=N * 24)
+        # normalising in place: after the first call w sums to 1, same work
+        ms = timed(lambda: gpu.normalize_weights(w), reps)
+        emit("normalize weights + ESS", f"{tag}: N={N}", ms, bytes_=N * 32)
+        ms = timed(lambda: gpu.inclusive_scan(w, out=out), reps)
+        emit("inclusive scan (cdf)", f"{tag}: N={N}", ms, bytes_=N * 24)
 
 
 def c5(reps):
