@@ -228,6 +228,31 @@ int abc_mvn_logpdf_direct(const double* x, int64_t M, const double* X,
                           const double* w, int64_t N, int d, const double* U,
                           int r, const double* V, int nv, double support_tol,
                           double log_const, double* out, void* stream);
+/* One KDE at G covariance scalings in one pass: the per-fold work of
+ * GridSearchCV (pyabc/transition/model_selection.py:9-74) over
+ * MultivariateNormalTransition.scaling, which multiplies the covariance
+ * (multivariatenormal.py:82), so every grid point shares the whitening U
+ * [d x r] of the covariance at scaling 1 (full rank, r = d <= 59):
+ *   out[g][i] = log sum_j w_j exp(-|(x_i - X_j) U|^2 inv_scaling[g] / 2)
+ *               + log_const[g],
+ *   log_const[g] = -(d log 2pi + log pdet_1 + d log s_g) / 2.
+ * inv_scaling, log_const: host arrays [G], 1 <= G <= 64 (launches of at most
+ * 8 grid points over one pair of operand images; a grid point's result does
+ * not depend on which others share its call).  The f64-MFMA arithmetic of
+ * abc_mvn_logpdf at ABC_PREC_F64 (2e-6) with a running exponent reference per
+ * (point, g): finite wherever the fp64 value is, -inf where every term of the
+ * reference's fp64 sum underflows (below ln 2^-1075) or every weight is 0.
+ * wt [M] (device, nullable) with score [G] (device, nullable; needs wt):
+ * score[g] = sum_i wt[i] out[g][i], Transition.score (base.py:114-116), fp64
+ * in a fixed order, plain IEEE products (0 * -inf = NaN).  The size query
+ * returns 0 for a shape the call rejects. */
+size_t abc_mvn_logpdf_scaled_bytes(int64_t M, int64_t N, int r, int G);
+int abc_mvn_logpdf_scaled(const double* x, int64_t M, int d, const double* X,
+                          const double* w, int64_t N, const double* mu,
+                          const double* U, int r, const double* inv_scaling,
+                          int G, const double* log_const, double* out,
+                          const double* wt, double* score, void* ws,
+                          size_t ws_bytes, void* stream);
 
 /* ---- proposal: Transition.rvs + prior support (smc.py:610-662) ----------
  * Candidate g (global index idx0 .. idx0+B-1) draws, from Philox4x32-10 keyed

@@ -38,7 +38,7 @@ from .model import (Model, SimpleModel, ModelResult, IntegratedModel,
                     VectorizedModel, LinearGaussianModel)
 from .transition import (Transition, MultivariateNormalTransition,
                          LocalTransition, DiscreteRandomWalkTransition,
-                         NotEnoughParticles)
+                         GridSearchCV, NotEnoughParticles)
 from .population import Particle, Population
 from .populationstrategy import (ConstantPopulationSize, PopulationStrategy,
                                  AdaptivePopulationSize, ListPopulationSize)

@@ -43,6 +43,9 @@ SIGNATURES = {
                              P, P, P, SZ, P]),
     "abc_mvn_logpdf_direct": (I32, [P, I64, P, P, I64, I32, P, I32, P, I32,
                                     D, D, P, P]),
+    "abc_mvn_logpdf_scaled_bytes": (SZ, [I64, I64, I32, I32]),
+    "abc_mvn_logpdf_scaled": (I32, [P, I64, I32, P, P, I64, P, P, I32, P, I32, P,
+                                    P, P, P, P, SZ, P]),
     "abc_cdf_guide": (I32, [P, I64, P, P]),
     "abc_ancestor_table_bytes": (I64, [I64, I32]),
     "abc_ancestor_table": (I32, [P, P, I64, I32, P, SZ, P]),

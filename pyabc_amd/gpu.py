@@ -272,6 +272,38 @@ def mvn_logpdf_direct(x, X, w, U, V, support_tol, log_const, out=None):
     return out
 
 
+def mvn_logpdf_scaled(xd, Xd, wd, mu, U, scalings, log_consts, wt=None):
+    """One KDE at G covariance scalings in one pass (abc_mvn_logpdf_scaled):
+    out [G, M] log densities of the points xd [M, d] under the population
+    (Xd, wd) whitened by U (the covariance at scaling 1, full rank), and
+    score [G] = sum_i wt[i] out[g, i] (None without wt).  scalings and
+    log_consts are host sequences of length G."""
+    import ctypes
+    M, d = xd.shape
+    N = Xd.shape[0]
+    r = U.shape[1]
+    s = np.ascontiguousarray(scalings, dtype=np.float64).ravel()
+    lc = np.ascontiguousarray(log_consts, dtype=np.float64).ravel()
+    G = s.size
+    if lc.size != G:
+        raise ValueError("mvn_logpdf_scaled: scalings and log_consts differ in length")
+    if G and not np.all(s > 0):
+        raise ValueError("mvn_logpdf_scaled: scalings must be positive")
+    if wt is not None and wt.numel() != M:
+        raise ValueError("mvn_logpdf_scaled: wt must have one entry per point")
+    inv = np.ascontiguousarray(1.0 / s) if G else s
+    out = torch.empty((G, M), dtype=F64, device=xd.device)
+    score = None if wt is None else torch.empty(G, dtype=F64, device=xd.device)
+    nb = nat.query("abc_mvn_logpdf_scaled_bytes", M, N, r, G)
+    ws = workspace(nb, "mvn")
+    nat.call("abc_mvn_logpdf_scaled", p(xd), M, d, p(Xd), p(wd), N, p(mu), p(U), r,
+             inv.ctypes.data_as(ctypes.c_void_p), G,
+             lc.ctypes.data_as(ctypes.c_void_p), p(out),
+             None if wt is None else p(wt), p(score), p(ws), ws.numel(),
+             stream_ptr())
+    return out, score
+
+
 # ---- proposal / prior / simulator / distance / acceptance ----------------
 
 def cdf_guide(cdf):

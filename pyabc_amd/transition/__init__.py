@@ -7,9 +7,10 @@ from .multivariatenormal import (MultivariateNormalTransition,
 from .local_transition import LocalTransition
 from .randomwalk import DiscreteRandomWalkTransition
 from .predict_population_size import predict_population_size, CVEstimate
+from .model_selection import GridSearchCV
 
 __all__ = ["Transition", "DiscreteTransition", "NotEnoughParticles",
            "MultivariateNormalTransition", "LocalTransition",
-           "DiscreteRandomWalkTransition",
+           "DiscreteRandomWalkTransition", "GridSearchCV",
            "silverman_rule_of_thumb", "scott_rule_of_thumb",
            "predict_population_size", "CVEstimate"]
