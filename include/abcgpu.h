@@ -452,6 +452,71 @@ int abc_pnorm_accept(const double* x, int64_t B, int S, const double* x0,
                      int max_attempts, int64_t cap, int64_t* idx, int64_t* count,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- several models per generation (model selection) ----------------------
+ * Replaces the model steps of _generate_valid_proposal (pyabc/smc.py:610-662)
+ * for runs with more than one model.  One model's proposal pieces: the
+ * per-model subset of abc_candidate_spec (same meaning field for field; HOST
+ * struct, device arrays). */
+typedef struct abc_model_desc {
+  int d;                       /* parameters of this model, 1 <= d <= 64     */
+  const double* X;             /* population [N x d]; NULL: prior draw        */
+  const double* cdf;           /* inclusive scan of the model's weights [N]   */
+  const int32_t* guide;        /* abc_cdf_guide table [N] (nullable)          */
+  int64_t N;
+  const double* L;             /* [d x d] lower-triangular, shared            */
+  const int32_t* prior_kind;   /* [d] ABC_PRIOR_*                             */
+  const double* prior_params;  /* [4 d]                                       */
+  const double* support_box;   /* [d x (lo, hi)] from abc_prior_support_box
+                                  (nullable: each call computes it)           */
+} abc_model_desc;
+/* Proposals of candidates idx0 .. idx0 + B - 1 over M models (1 <= M <= 16;
+ * models, model_cdf: HOST arrays [M]).  t > 0 (smc.py:636-662): the reference
+ * draws a source model m ~ p(t-1) over the alive models, the target m' ~
+ * K(. | m) (ModelPerturbationKernel, random_variables.py:455-538), starts
+ * again while m' is dead (smc.py:641-649), draws theta ~ T_m'.rvs() and starts
+ * the whole attempt again -- the model included -- while model_prior(m')
+ * prior_m'(theta) is 0 (smc.py:654-656).  The model steps are one categorical
+ * draw from q~(m') ~ sum_m p_m K(m' | m) over the alive m' of positive prior
+ * mass: model_cdf is its inclusive scan (not normalised); a model of zero mass
+ * is never drawn.  t = 0 (smc.py:624-626): X == NULL in every descriptor,
+ * model_cdf the scan of the model prior's pmf, theta ~ prior_m.
+ * Per candidate g and attempt a: model = np.searchsorted(model_cdf, u *
+ * model_cdf[M-1], side="right") with u the 53-bit uniform of words 0, 1 of
+ * Philox slot a * 65536 + 65535 (no draw of theta reaches that slot); theta in
+ * that model by abc_propose's attempt a (same streams, same arithmetic, same
+ * support test), so M = 1 gives abc_propose's rows bit for bit.
+ * Writes model [B], theta [B x d_max] (d_max = the largest d; columns >= d_m
+ * NaN), ancestor [B] (row of the model's own population; -1 for the prior
+ * draw) and attempts [B] (max_attempts + 1: gave up; model and theta are then
+ * the last attempt's). */
+int abc_models_propose(const abc_model_desc* models, int M, const double* model_cdf,
+                       uint64_t seed, uint32_t generation, int64_t idx0, int64_t B,
+                       int max_attempts, int32_t* model, double* theta,
+                       int64_t* ancestor, int32_t* attempts, void* stream);
+/* abc_simulate_linear_gaussian (the Model.sample boundary, pyabc/model.py:
+ * 89-116, called for the proposal's model at smc.py:664-724) with row b's
+ * model choosing its tables: src, a, sigma [M x S] (device), theta [B x d_max],
+ * x[b,k] = a[m,k] theta[b, src[m,k]] + sigma[m,k] e, the same noise stream
+ * (slot 0x40000000 + k/4 of candidate idx0 + b).  A row whose model is outside
+ * [0, M) is NaN. */
+int abc_models_simulate_linear_gaussian(const double* theta, const int32_t* model,
+                                        int64_t B, int d_max, int M, int S,
+                                        const int32_t* src, const double* a,
+                                        const double* sigma, uint64_t seed,
+                                        uint32_t generation, int64_t idx0, double* x,
+                                        void* stream);
+/* Stable split of positions 0 .. B-1 by model id (the per-model stores of
+ * Population.to_dict / _normalize_weights, pyabc/population.py:123-145,
+ * 264-289, and of History.append_population): perm [B] = the positions
+ * grouped by model, increasing within a model (np.argsort(model,
+ * kind="stable")); counts [M] (device int64) = rows per model.  Tile counts,
+ * one scan, one scatter: no atomic decides an order.  An id outside [0, M)
+ * returns ABC_ERR_INVALID (perm is then unspecified); to report it the call
+ * waits for the stream.  Scratch: abc_models_partition_bytes(B, M) bytes. */
+size_t abc_models_partition_bytes(int64_t B, int M);
+int abc_models_partition(const int32_t* model, int64_t B, int M, int64_t* perm,
+                         int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- AggregatedDistance.__call__ (pyabc/distance/distance.py:434-461) with
  * PNormDistance children (distance.py:79-105) -------------------------------
  * A term stack is K p-norm terms over the same row x[b, :] of x [B x S]:

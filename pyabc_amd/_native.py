@@ -65,6 +65,11 @@ SIGNATURES = {
     "abc_candidates_round": (I32, [P, I64, I64, D, P, D, I32, I64, P, P, P, P, SZ, P]),
     "abc_candidates_regen": (I32, [P, I64, P, I64, P, P, P, P, P, P, P]),
     "abc_pnorm_accept": (I32, [P, I64, I32, P, P, D, D, P, I32, I64, P, P, P, SZ, P]),
+    "abc_models_propose": (I32, [P, I32, P, U64, U32, I64, I64, I32, P, P, P, P, P]),
+    "abc_models_simulate_linear_gaussian": (I32, [P, P, I64, I32, I32, I32, P, P, P,
+                                                  U64, U32, I64, P, P]),
+    "abc_models_partition_bytes": (SZ, [I64, I32]),
+    "abc_models_partition": (I32, [P, I64, I32, P, P, P, SZ, P]),
     "abc_aggregate_distance": (I32, [P, I64, I32, P, P, P, P, I32, P, P, P]),
     "abc_aggregate_accept": (I32, [P, I64, I32, P, P, P, P, I32, D, P, I32, I64, P, P, P,
                                    SZ, P]),
@@ -127,6 +132,15 @@ class CandidateSpec(C.Structure):
                 ("seed", U64), ("generation", U32), ("anc_table", P),
                 ("support_box", P)]
 
+
+class ModelDesc(C.Structure):
+    """abc_model_desc (include/abcgpu.h), field for field."""
+    _fields_ = [("d", C.c_int), ("X", P), ("cdf", P), ("guide", P), ("N", I64),
+                ("L", P), ("prior_kind", P), ("prior_params", P),
+                ("support_box", P)]
+
+
+ABC_MODELS_MAX = 16
 
 # C error codes (include/abcgpu.h)
 ABC_OK = 0

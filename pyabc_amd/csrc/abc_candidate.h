@@ -24,6 +24,10 @@ namespace abc {
 constexpr double LOG_SQRT_2PI = 0.91893853320467274178;
 constexpr uint32_t SLOTS_PER_ATTEMPT = 65536;
 constexpr uint32_t SLOT_ANCESTOR = 0;
+// several models (abc_models.hip): the attempt's model draw, words 0, 1 of the
+// attempt's last slot (perturbation slots end at 16, prior slots at
+// 32 + 512 * 63 + 511 for d <= 64: no draw of theta reaches it)
+constexpr uint32_t SLOT_MODEL = SLOTS_PER_ATTEMPT - 1;
 constexpr uint32_t SLOT_PERTURB = 1;     // 4 normals per slot (after the first two)
 constexpr uint32_t SLOT_PRIOR = 32;      // + 512 k + iteration
 constexpr uint32_t SLOT_SIM = 0x40000000u;
@@ -532,92 +536,105 @@ __device__ __forceinline__ void stage_block_consts(BlockConsts& C, const Proposa
   __syncthreads();
 }
 
-// Candidate g: ancestor j ~ Cat(w), theta = X_j + L_j n (or a prior draw when
-// X == nullptr), re-drawn while theta is outside the prior support C.box.
-// th holds D (D > 0) or d <= 64 values.  The perturbation is accumulated one
-// Box-Muller pair at a time in q order, theta_k = fma(L_kq, n_q, theta_k)
-// starting from X_jk (one code copy of the transform).  Returns the attempts
-// used, max_attempts + 1 when every attempt fell outside the support (theta
-// then holds the last one).
+// One attempt `att` of candidate g's proposal: ancestor j ~ Cat(w), theta =
+// X_j + L_j n (or a prior draw in PROP_PRIOR), and whether theta lies in the
+// prior support C.box.  th holds D (D > 0) or d <= 64 values.  The
+// perturbation is accumulated one Box-Muller pair at a time in q order,
+// theta_k = fma(L_kq, n_q, theta_k) starting from 0, then X_jk + (L n)_k (one
+// code copy of the transform).  The single definition of an attempt: the
+// single-model re-draw loop (propose_one) and the multi-model one
+// (abc_models.hip, which draws the model anew before every attempt) both
+// inline it.  C: the block's constants (BlockConsts, or any type with its
+// bmt, LT, box and inv_step: LT is read only when D is staged, 0 < D <=
+// LT_DMAX in PROP_MVN, inv_step only with TABLE); total = cdf[N - 1].
+template <int D, int MODE, bool TABLE = false, class CT>
+__device__ __forceinline__ bool propose_attempt(const ProposalArgs& A, const CT& C, double total,
+                                                uint64_t g, int att, double* th, int64_t& j) {
+  constexpr bool LT_LDS = MODE == PROP_MVN && D > 0 && D <= LT_DMAX;
+  const int d = D > 0 ? D : A.d;
+  const uint32_t s0 = (uint32_t)att * SLOTS_PER_ATTEMPT;
+  // an opaque zero offset on the LDS constants: without it the compiler
+  // hoists the loop-invariant L / box reads out of the caller's candidate
+  // loop into ~100 registers and halves the occupancy
+  int oz = 0;
+  asm volatile("" : "+s"(oz));
+  const double* LT = C.LT + oz;
+  const double* box = C.box + oz;
+  if (MODE == PROP_PRIOR) {
+#pragma unroll
+    for (int k = 0; k < (D > 0 ? D : d); ++k)
+      th[k] = prior_draw1(A.kind[k], A.params + 4 * k, g,
+                          s0 + SLOT_PRIOR + 512u * k, A.gen, A.seed);
+  } else {
+    // the ancestor's guide bracket is loaded first and the perturbation
+    // L n (independent of j) is computed while those loads are in flight;
+    // the search and the X_j row come after: theta_k = X_jk + (L n)_k
+    const u32x4 ra = philox(g, s0 + SLOT_ANCESTOR, A.gen, A.seed);
+    u32x4 r = ra;
+    const double target = uniform53(ra.x, ra.y) * total;
+    AncestorBracket br;
+    if (TABLE) {
+      const int64_t kt = anc_bin(target, C.inv_step, A.G);
+      br = {A.bguide[kt], A.bguide[kt + 1]};  // answer in [lo, hi]
+    } else {
+      br = ancestor_bracket(A.guide, A.N, total, target);
+    }
+#pragma unroll
+    for (int k = 0; k < (D > 0 ? D : d); ++k) th[k] = 0.0;
+    const double* Lj = A.L;
+    if (MODE == PROP_LOCAL) {
+      // per-particle factor: needs j first
+      j = TABLE ? table_finish(A.rec, A.rs, d, A.N, target, br)
+                : ancestor_finish(A.cdf, A.N, target, br);
+      Lj = A.L + j * d * d;
+    }
+    // L is lower triangular (a Cholesky factor; the ABI contract), so
+    // column q only reaches rows k >= q: with D known the pair loop is
+    // unrolled and the upper triangle's multiply-adds vanish
+    auto pair = [&](int q) {
+      uint32_t wa, wb;
+      perturb_words(q >> 1, ra, r, g, s0, A.gen, A.seed, wa, wb);
+      double n0, n1;
+      box_muller(wa, wb, n0, n1, C.bmt);
+      const bool two = q + 1 < d;
+#pragma unroll
+      for (int k = 0; k < (D > 0 ? D : d); ++k) {
+        if (k >= q) {
+          const double l0 = LT_LDS ? LT[q * d + k] : Lj[k * d + q];
+          th[k] = fma(l0, n0, th[k]);
+        }
+        if (two && k >= q + 1) {
+          const double l1 = LT_LDS ? LT[(q + 1) * d + k] : Lj[k * d + q + 1];
+          th[k] = fma(l1, n1, th[k]);
+        }
+      }
+    };
+#pragma unroll 1
+    for (int q = 0; q < d; q += 2) pair(q);
+    if (MODE != PROP_LOCAL)
+      j = TABLE ? table_finish(A.rec, A.rs, d, A.N, target, br)
+                : ancestor_finish(A.cdf, A.N, target, br);
+    const double* Xj = TABLE ? A.rec + j * A.rs : A.X + j * d;
+#pragma unroll
+    for (int k = 0; k < (D > 0 ? D : d); ++k) th[k] = Xj[k] + th[k];
+  }
+  bool ok = true;  // branch-free (&& would branch per comparison)
+#pragma unroll
+  for (int k = 0; k < (D > 0 ? D : d); ++k)
+    ok = ok & (box[2 * k] <= th[k]) & (th[k] <= box[2 * k + 1]);
+  return ok;  // prior density > 0 (smc.py:654-656)
+}
+
+// Candidate g: attempts (propose_attempt) re-drawn while theta is outside the
+// prior support C.box.  Returns the attempts used, max_attempts + 1 when every
+// attempt fell outside the support (theta then holds the last one).
 template <int D, int MODE, bool TABLE = false>
 __device__ __forceinline__ int propose_one(const ProposalArgs& A, const BlockConsts& C,
                                            uint64_t g, double* th, int64_t& j) {
-  constexpr bool LT_LDS = MODE == PROP_MVN && D > 0 && D <= LT_DMAX;
-  const int d = D > 0 ? D : A.d;
   j = -1;
   const double total = C.total;
   for (int att = 0; att < A.max_attempts; ++att) {
-    const uint32_t s0 = (uint32_t)att * SLOTS_PER_ATTEMPT;
-    // an opaque zero offset on the LDS constants: without it the compiler
-    // hoists the loop-invariant L / box reads out of the caller's candidate
-    // loop into ~100 registers and halves the occupancy
-    int oz = 0;
-    asm volatile("" : "+s"(oz));
-    const double* LT = C.LT + oz;
-    const double* box = C.box + oz;
-    if (MODE == PROP_PRIOR) {
-#pragma unroll
-      for (int k = 0; k < (D > 0 ? D : d); ++k)
-        th[k] = prior_draw1(A.kind[k], A.params + 4 * k, g,
-                            s0 + SLOT_PRIOR + 512u * k, A.gen, A.seed);
-    } else {
-      // the ancestor's guide bracket is loaded first and the perturbation
-      // L n (independent of j) is computed while those loads are in flight;
-      // the search and the X_j row come after: theta_k = X_jk + (L n)_k
-      const u32x4 ra = philox(g, s0 + SLOT_ANCESTOR, A.gen, A.seed);
-      u32x4 r = ra;
-      const double target = uniform53(ra.x, ra.y) * total;
-      AncestorBracket br;
-      if (TABLE) {
-        const int64_t kt = anc_bin(target, C.inv_step, A.G);
-        br = {A.bguide[kt], A.bguide[kt + 1]};  // answer in [lo, hi]
-      } else {
-        br = ancestor_bracket(A.guide, A.N, total, target);
-      }
-#pragma unroll
-      for (int k = 0; k < (D > 0 ? D : d); ++k) th[k] = 0.0;
-      const double* Lj = A.L;
-      if (MODE == PROP_LOCAL) {
-        // per-particle factor: needs j first
-        j = TABLE ? table_finish(A.rec, A.rs, d, A.N, target, br)
-                  : ancestor_finish(A.cdf, A.N, target, br);
-        Lj = A.L + j * d * d;
-      }
-      // L is lower triangular (a Cholesky factor; the ABI contract), so
-      // column q only reaches rows k >= q: with D known the pair loop is
-      // unrolled and the upper triangle's multiply-adds vanish
-      auto pair = [&](int q) {
-        uint32_t wa, wb;
-        perturb_words(q >> 1, ra, r, g, s0, A.gen, A.seed, wa, wb);
-        double n0, n1;
-        box_muller(wa, wb, n0, n1, C.bmt);
-        const bool two = q + 1 < d;
-#pragma unroll
-        for (int k = 0; k < (D > 0 ? D : d); ++k) {
-          if (k >= q) {
-            const double l0 = LT_LDS ? LT[q * d + k] : Lj[k * d + q];
-            th[k] = fma(l0, n0, th[k]);
-          }
-          if (two && k >= q + 1) {
-            const double l1 = LT_LDS ? LT[(q + 1) * d + k] : Lj[k * d + q + 1];
-            th[k] = fma(l1, n1, th[k]);
-          }
-        }
-      };
-#pragma unroll 1
-      for (int q = 0; q < d; q += 2) pair(q);
-      if (MODE != PROP_LOCAL)
-        j = TABLE ? table_finish(A.rec, A.rs, d, A.N, target, br)
-                  : ancestor_finish(A.cdf, A.N, target, br);
-      const double* Xj = TABLE ? A.rec + j * A.rs : A.X + j * d;
-#pragma unroll
-      for (int k = 0; k < (D > 0 ? D : d); ++k) th[k] = Xj[k] + th[k];
-    }
-    bool ok = true;  // branch-free (&& would branch per comparison)
-#pragma unroll
-    for (int k = 0; k < (D > 0 ? D : d); ++k)
-      ok = ok & (box[2 * k] <= th[k]) & (th[k] <= box[2 * k + 1]);
-    if (ok) return att + 1;  // prior density > 0 (smc.py:654-656)
+    if (propose_attempt<D, MODE, TABLE>(A, C, total, g, att, th, j)) return att + 1;
   }
   return A.max_attempts + 1;
 }

@@ -669,6 +669,103 @@ class CandidateRound:
                      int(n), p(n_dev), *ptrs, stream_ptr())
 
 
+class ModelSet:
+    """The proposal pieces of a generation's M models for abc_models_propose
+    (an abc_model_desc array on the host plus the tensors it points to).
+    ``models``: one dict per model with d, prior_kind (int32 [d]),
+    prior_params [4 d] and, for a transition proposal, X [N, d], cdf [N], L
+    [d, d] and optionally guide (int32 [N]); ``model_cdf``: the inclusive scan
+    of the model masses (host, [M])."""
+
+    def __init__(self, models, model_cdf, seed, generation, max_attempts):
+        M = len(models)
+        if not 1 <= M <= nat.ABC_MODELS_MAX:
+            raise ValueError(f"ModelSet: 1 <= M <= {nat.ABC_MODELS_MAX} models")
+        self.M = M
+        self.desc = (nat.ModelDesc * M)()
+        self.model_cdf = np.ascontiguousarray(model_cdf, dtype=np.float64)
+        if self.model_cdf.shape != (M,):
+            raise ValueError("ModelSet: model_cdf needs one entry per model")
+        self._keep = []
+        self.d = []
+        for s, m in zip(self.desc, models):
+            d = int(m["d"])
+            kind, params = m["prior_kind"], m["prior_params"]
+            if kind.dtype != torch.int32 or kind.numel() != d or params.numel() != 4 * d:
+                raise TypeError("ModelSet: prior_kind int32 [d], prior_params [4 d]")
+            X = m.get("X")
+            if X is not None and (X.dim() != 2 or X.shape[1] != d
+                                  or m["cdf"].numel() != X.shape[0]
+                                  or m["L"].numel() != d * d):
+                raise ValueError("ModelSet: X [N, d], cdf [N], L [d, d]")
+            box = torch.empty(2 * d, dtype=F64, device=params.device)
+            nat.call("abc_prior_support_box", p(kind), p(params), d, p(box), stream_ptr())
+            ts = [kind, params, box] + ([] if X is None else
+                                        [X, m["cdf"], m["L"], m.get("guide")])
+            for t in ts:
+                if t is not None:
+                    assert t.is_contiguous() and t.is_cuda
+                    self._keep.append(t)
+            s.d = d
+            s.X, s.cdf, s.guide = _ptr(X), _ptr(m.get("cdf")), _ptr(m.get("guide"))
+            s.N = 0 if X is None else int(X.shape[0])
+            s.L = _ptr(m.get("L"))
+            s.prior_kind, s.prior_params, s.support_box = p(kind), p(params), p(box)
+            self.d.append(d)
+        self.d_max = max(self.d)
+        self.device = models[0]["prior_params"].device
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.generation = int(generation) & 0xFFFFFFFF
+        self.max_attempts = int(max_attempts)
+
+    def propose(self, idx0, B):
+        """Candidates idx0 .. idx0 + B - 1 (abc_models_propose): model [B]
+        int32, theta [B, d_max] (NaN past the model's d), ancestor [B] int64
+        (-1 for a prior draw), attempts [B] int32."""
+        import ctypes as C
+        B, dev = int(B), self.device
+        model = torch.empty(B, dtype=torch.int32, device=dev)
+        theta = torch.empty((B, self.d_max), dtype=F64, device=dev)
+        anc = torch.empty(B, dtype=I64, device=dev)
+        att = torch.empty(B, dtype=torch.int32, device=dev)
+        nat.call("abc_models_propose", C.addressof(self.desc), self.M,
+                 self.model_cdf.ctypes.data, self.seed, self.generation, int(idx0), B,
+                 self.max_attempts, p(model) if B else None, p(theta) if B else None,
+                 p(anc) if B else None, p(att) if B else None, stream_ptr())
+        return model, theta, anc, att
+
+
+def models_simulate_linear_gaussian(theta, model, src, a, sigma, seed, generation,
+                                    idx0, out=None):
+    """abc_models_simulate_linear_gaussian: theta [B, d_max], model [B] int32,
+    src (int32), a, sigma [M, S] -> x [B, S]."""
+    B, dmax = theta.shape
+    M, S = src.shape
+    out = torch.empty((B, S), dtype=F64, device=theta.device) if out is None else out
+    if B:
+        nat.call("abc_models_simulate_linear_gaussian", p(theta), p(model), int(B),
+                 int(dmax), int(M), int(S), p(src), p(a), p(sigma),
+                 int(seed) & (2 ** 64 - 1), int(generation) & 0xFFFFFFFF, int(idx0),
+                 p(out), stream_ptr())
+    return out
+
+
+def models_partition(model, M):
+    """abc_models_partition: (perm [B] int64, the positions grouped by model id
+    and increasing within a model; counts [M] int64, device) of model [B]
+    int32.  ValueError for an id outside [0, M)."""
+    B = model.numel()
+    if model.dtype != torch.int32:
+        raise TypeError("models_partition: model ids must be int32")
+    perm = torch.empty(B, dtype=I64, device=model.device)
+    counts = torch.empty(int(M), dtype=I64, device=model.device)
+    nb = nat.query("abc_models_partition_bytes", int(B), int(M))
+    ws = workspace(nb, "partition")
+    nat.call("abc_models_partition", p(model) if B else None, int(B), int(M),
+             p(perm) if B else None, p(counts), p(ws), ws.numel(), stream_ptr())
+    return perm, counts
+
+
 def round_keep(counts, need, rank, out=None):
     """abc_round_keep: this rank's kept rows of a round (device int64 [1])
     from the all-gathered per-rank accept counts (device int64 [ws])."""

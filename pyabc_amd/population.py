@@ -75,7 +75,30 @@ class WeightedDistances:
 
 
 class Population:
-    def __init__(self, particles: List[Particle] = None, columns=None):
+    def __init__(self, particles: List[Particle] = None, columns=None,
+                 model_columns=None):
+        self._mcols = None
+        if model_columns is not None:
+            # several models: {m: ColumnarParticles}, every model's particles
+            # in candidate order.  _normalize_weights (population.py:123-145)
+            # on the device per model; the model probabilities are host
+            # arithmetic on M weight sums
+            from . import gpu
+            self._cols = None
+            self._list = None
+            self._mcols = {int(m): c for m, c in sorted(model_columns.items())
+                           if len(c)}
+            stats = {m: gpu.normalize_weights(c.weights)
+                     for m, c in self._mcols.items()}
+            host = gpu.torch.stack([stats[m] for m in self._mcols]).cpu().numpy()
+            total = float(host[:, 0].sum())
+            self._model_probabilities = {
+                m: float(host[k, 0]) / total for k, m in enumerate(self._mcols)}
+            # ESS of the population weights w p_m: 1 / sum_m p_m^2 sum w_m^2
+            self._ess = 1.0 / sum(
+                self._model_probabilities[m] ** 2 / float(host[k, 1])
+                for k, m in enumerate(self._mcols))
+            return
         if columns is not None:
             self._cols = columns
             self._list = None
@@ -93,14 +116,39 @@ class Population:
     def from_columns(cls, columns: ColumnarParticles):
         return cls(columns=columns)
 
+    @classmethod
+    def from_model_columns(cls, model_columns: dict):
+        return cls(model_columns=model_columns)
+
     @property
     def columns(self):
         return self._cols
 
+    @property
+    def model_columns(self):
+        """{m: ColumnarParticles} of a device population over several models
+        (None otherwise; ``columns`` stays the single-model form)."""
+        return self._mcols
+
     def __len__(self):
+        if self._mcols is not None:
+            return sum(len(c) for c in self._mcols.values())
         return len(self._cols) if self._cols is not None else len(self._list)
 
     def _materialise(self):
+        if self._list is None and self._mcols is not None:
+            self._list = []
+            for m, c in self._mcols.items():
+                th = c.theta.cpu().numpy()
+                w = c.weights.cpu().numpy()
+                dist = c.distances.cpu().numpy()
+                ss = c.sum_stats.cpu().numpy()
+                self._list.extend(
+                    Particle(m=m, parameter=Parameter(dict(zip(c.param_names, th[i]))),
+                             weight=float(w[i]),
+                             accepted_sum_stats=[dict(zip(c.sum_stat_keys, ss[i]))],
+                             accepted_distances=[float(dist[i])])
+                    for i in range(len(c)))
         if self._list is None:
             c = self._cols
             th = c.theta.cpu().numpy()
@@ -142,19 +190,35 @@ class Population:
             from . import gpu
             d = np.array([p.accepted_distances[0] for p in self._list])
             self._cols.distances = gpu.as_dev(d, device=self._cols.theta.device)
+        if self._mcols is not None:
+            # (_materialise lists the particles model by model)
+            from . import gpu
+            d = np.array([p.accepted_distances[0] for p in self._list])
+            off = 0
+            for c in self._mcols.values():
+                c.distances = gpu.as_dev(d[off:off + len(c)], device=c.theta.device)
+                off += len(c)
 
     def update_distances_device(self, distance, x0vec, t):
         """Batched re-evaluation of the accepted distances (population.py:
         147-162) after the distance changed: one abc_pnorm launch."""
-        c = self._cols
-        c.distances = distance.device_call(c.sum_stats, x0vec, t,
-                                           c.sum_stat_keys)
+        for c in ([self._cols] if self._mcols is None else self._mcols.values()):
+            c.distances = distance.device_call(c.sum_stats, x0vec, t,
+                                               c.sum_stat_keys)
         self._list = None
 
     def get_model_probabilities(self) -> dict:
         return self._model_probabilities
 
     def get_weighted_distances(self):
+        if self._mcols is not None:
+            # w p_m, the models concatenated in model order
+            from . import gpu
+            cs = self._mcols
+            return WeightedDistances(
+                gpu.torch.cat([c.distances for c in cs.values()]),
+                gpu.torch.cat([c.weights * self._model_probabilities[m]
+                               for m, c in cs.items()]))
         if self._cols is not None:
             # single model: model probability 1
             return WeightedDistances(self._cols.distances, self._cols.weights)
@@ -176,6 +240,12 @@ class Population:
         return weights, sum_stats
 
     def get_accepted_sum_stats(self):
+        if self._mcols is not None:
+            from . import gpu
+            from .distance.distance import SumStatMatrix
+            cs = list(self._mcols.values())
+            return SumStatMatrix(gpu.torch.cat([c.sum_stats for c in cs]),
+                                 cs[0].sum_stat_keys)
         if self._cols is not None and self._cols.sum_stats is not None:
             from .distance.distance import SumStatMatrix
             return SumStatMatrix(self._cols.sum_stats, self._cols.sum_stat_keys)

@@ -102,6 +102,25 @@ class ColumnarSample:
         return parts[:m]
 
 
+class ModelsSample(ColumnarSample):
+    """ColumnarSample over several models: {m: ColumnarParticles}."""
+
+    def __init__(self, model_columns, recorded, recorded_keys, record_rejected, ok):
+        super().__init__(None, recorded, recorded_keys, record_rejected, ok)
+        self._mcols = model_columns
+
+    @property
+    def n_accepted(self):
+        return sum(len(c) for c in self._mcols.values())
+
+    def get_accepted_population(self):
+        return Population.from_model_columns(self._mcols)
+
+    def first_m_particles(self, m):
+        parts = self.get_accepted_population().get_list()
+        return parts if m is None or not np.isfinite(m) else parts[:int(m)]
+
+
 class _PinnedReader:
     """Device int64 values read on the host with one wait: queue() copies
     them into a cached pinned buffer (async copies, no concatenation kernel,
@@ -263,9 +282,11 @@ class _RoundLedger:
 
 
 class BatchedGPUSampler(Sampler):
-    """Batched, device-resident sampler (single model, nr_samples_per_param 1).
-    Closures outside that (a plain ``simulate_one``, a scalar model, ...) run
-    the reference's per-candidate loop instead (_sample_per_candidate).
+    """Batched, device-resident sampler (nr_samples_per_param 1): fused or
+    staged rounds for one model, staged multi-model rounds for 2 to 16 models
+    (_sample_models).  Closures outside that (a plain ``simulate_one``, a
+    scalar model, ...) run the reference's per-candidate loop instead
+    (_sample_per_candidate).
 
     Parameters
     ----------
@@ -383,6 +404,9 @@ class BatchedGPUSampler(Sampler):
         seed = self._base_seed(dev)
         gen = spec.t & 0xFFFFFFFF
         record = self.sample_factory.record_rejected
+        if getattr(spec, "models", None) is not None:
+            return self._sample_models(n, spec, max_eval, record, dev, seed, gen,
+                                       all_accepted)
         d = len(spec.param_names)
         fr = None if all_accepted else self._fused_round(spec, seed, gen, dev)
         if fr is not None:
@@ -508,6 +532,157 @@ class BatchedGPUSampler(Sampler):
             self._acc_rate = max(int(counts.sum()) / float(ws * B), 1e-6)
         return self._finish(spec, led, kept, rec_x if record else None, rec_extra,
                             dev, d, all_accepted)
+
+    # ---- several models --------------------------------------------------
+    def _sample_models(self, n, spec, max_eval, record, dev, seed, gen, all_accepted):
+        """sample_until_n_accepted over M > 1 models (staged rounds, one
+        rank).  A round proposes (model, theta) per candidate
+        (abc_models_propose: the reference's model steps and whole-attempt
+        re-draw, smc.py:610-662), simulates every row under its model,
+        applies the staged loop's accept step to the statistics and keeps
+        the first n accepted in candidate order; the kept rows are split by
+        model at the end and weighted per model (smc.py:754-811):
+        w = pi(m) prior_m(theta) / (model_factor(m) T_m(theta))."""
+        torch = gpu.torch
+        ms = spec.models
+        M, S, dmax = ms["M"], len(spec.sum_stat_keys), max(ms["d"])
+        descs = []
+        for m in range(M):
+            desc = dict(d=ms["d"][m], prior_kind=ms["prior_kind"][m],
+                        prior_params=ms["prior_params"][m])
+            tr = ms["transitions"][m]
+            if tr is not None:
+                desc.update(X=tr._dev_X, cdf=tr._dev_cdf, guide=tr._dev_guide, L=tr._dev_L)
+            descs.append(desc)
+        mset = gpu.ModelSet(descs, ms["model_cdf"], seed, gen, self.max_attempts)
+        sims = [mod.fused_simulator(dev) if hasattr(mod, "fused_simulator") else None
+                for mod in ms["vmodels"]]
+        tables = None
+        if all(sim is not None for sim in sims):
+            tables = tuple(torch.stack([sim[k] for sim in sims]).contiguous()
+                           for k in range(3))
+        unfiltered = all_accepted or spec.distance is None
+        tail = None
+        if not unfiltered and self.accept_tail:
+            tail = self._accept_tail(spec, dev)
+        led = self._ledger(n, 0, 1, S)
+        kept = {k: [] for k in ("model", "theta", "dist", "x", "anc")}
+        rec_x = []
+        while led.need > 0:
+            if self.check_max_eval and led.n_eval >= max_eval:
+                break
+            B = self._limit_to_max_eval(self._round_size(led.need, 1, dmax, S),
+                                        max_eval, led.n_eval, 1)
+            kk = min(led.need, B)
+            lo = led.base
+            model, theta, anc, att = mset.propose(lo, B)
+            if tables is not None:
+                x = gpu.models_simulate_linear_gaussian(theta, model, *tables, seed, gen, lo)
+            else:
+                x = self._simulate_by_model(ms, model, theta, seed, gen, lo, S)
+            dist = None
+            if tail is not None:
+                idx, cnt = tail.accept(x, spec.x0vec, spec.eps, kk, att=att,
+                                       max_attempts=self.max_attempts)
+            elif unfiltered:
+                dist = torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
+                idx = torch.arange(B, dtype=gpu.I64, device=dev)
+            else:
+                dist = spec.distance.device_call(x, spec.x0vec, spec.t, spec.sum_stat_keys)
+                gpu.mask_gave_up(dist, att, self.max_attempts)
+                idx, cnt = gpu.accept_compact(dist, spec.eps)
+            if unfiltered:
+                cnt_local, pos = B, kk - 1
+            else:
+                nth = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
+                cnt_local, pos = torch.cat([cnt.view(1), nth]).cpu().tolist()
+            counts = dd.allgather_counts(cnt_local, dev)
+            k_mine, rec_rows = led.settle(counts, B, idx, pos, record)
+            if k_mine:
+                # model and ancestor travel as 8-byte columns of one gather
+                cols = [theta, x, anc, model.to(gpu.I64)] + ([] if dist is None else [dist])
+                got = gpu.gather_rows_batch(cols, idx[:k_mine])
+                if dist is None:
+                    got.append(tail.distances(got[1], spec.x0vec))
+                for k, v in zip(("theta", "x", "anc", "model", "dist"), got):
+                    kept[k].append(v)
+            if record:
+                rec_x.append(x[:rec_rows].clone() if rec_rows < B // 2 else x[:rec_rows])
+            self._acc_rate = max(int(counts.sum()) / float(B), 1e-6)
+        cols = self._assemble_models(spec, kept, dev, all_accepted)
+        self.nr_evaluations_ = int(led.n_eval)
+        per_model = {m: len(c) for m, c in cols.items()}
+        self.last_stats = dict(rounds=led.rounds, evaluations=int(led.n_eval),
+                               accepted=int(led.n_acc), models=M,
+                               accepted_per_model=per_model,
+                               records_truncated=led.records_truncated)
+        recorded = None
+        if record:
+            recorded = self._gather_recorded(rec_x, led.rec_keeps, dev, 1)
+        elif cols:
+            recorded = torch.cat([c.sum_stats for c in cols.values()])
+        return ModelsSample(cols, recorded, spec.sum_stat_keys, record,
+                            led.n_acc == led.n)
+
+    @staticmethod
+    def _simulate_by_model(ms, model, theta, seed, gen, lo, S):
+        """User VectorizedModels: the round's rows are split by model
+        (abc_models_partition), each model simulates its own rows [B_m, d_m]
+        in one call and the statistics return to their rows.  The groups
+        tile the round's index range (model m's rows take lo + offset_m ..),
+        so every row keeps an index of its own within the generation."""
+        torch = gpu.torch
+        B = theta.shape[0]
+        perm, counts = gpu.models_partition(model, ms["M"])
+        x = torch.empty((B, S), dtype=gpu.F64, device=theta.device)
+        off = 0
+        for m, c in enumerate(counts.cpu().tolist()):
+            if c == 0:
+                continue
+            sel = perm[off:off + c]
+            th = gpu.gather_rows(theta, sel)[:, :ms["d"][m]].contiguous()
+            xm = ms["vmodels"][m].simulate_batch(th, seed, gen, lo + off)
+            x[sel] = xm.to(gpu.F64)
+            off += c
+        return x
+
+    def _assemble_models(self, spec, kept, dev, all_accepted):
+        """{m: ColumnarParticles} of the kept rows: split by model (stable,
+        so every model's particles stay in candidate order) and weighted per
+        model on its own segment."""
+        torch = gpu.torch
+        ms = spec.models
+        if not kept["theta"]:
+            return {}
+        theta, x, anc, model, dist = (
+            v[0] if len(v) == 1 else torch.cat(v)
+            for v in (kept[k] for k in ("theta", "x", "anc", "model", "dist")))
+        perm, counts = gpu.models_partition(model.to(torch.int32), ms["M"])
+        out, off, queued = {}, 0, False
+        for m, c in enumerate(counts.cpu().tolist()):
+            if c == 0:
+                continue
+            th, xm, dm, am = gpu.gather_rows_batch([theta, x, dist, anc], perm[off:off + c])
+            off += c
+            th = th[:, :ms["d"][m]].contiguous()
+            tr = ms["transitions"][m]
+            if all_accepted or tr is None:
+                # calibration, t = 0: w = n_acc / n_per_param = 1
+                w = torch.ones(c, dtype=gpu.F64, device=dev)
+            else:
+                lp = gpu.prior_logpdf(th, ms["prior_kind"][m], ms["prior_params"][m])
+                lt = tr.logpdf_device(th, hint=am)
+                queued = True
+                w = gpu.importance_weights(
+                    lp, lt, spec.weight_scale * math.exp(ms["log_scale"][m]))
+            out[m] = ColumnarParticles(th, w, dm.contiguous(), xm.contiguous(),
+                                       ms["param_names"][m], spec.sum_stat_keys, m=m)
+        if queued:
+            # the previous generation's host reads, behind the densities
+            hook, self.on_density_queued = self.on_density_queued, None
+            if hook is not None:
+                hook()
+        return out
 
     @staticmethod
     def _accept_tail(spec, dev):

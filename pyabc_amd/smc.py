@@ -71,7 +71,13 @@ class GenerationSpec:
         if isinstance(abc.acceptor, StochasticAcceptor) and not all_accepted:
             self.stochastic = abc.acceptor.device_config(t, self.eps)
         self._closure = None
-        self._init_device(abc)
+        # several models: the per-model description (_init_models), None for
+        # a single model, whose path below is untouched
+        self.models = None
+        if len(abc.models) > 1:
+            self._init_models(abc)
+        else:
+            self._init_device(abc)
 
     @property
     def eps(self):
@@ -145,6 +151,114 @@ class GenerationSpec:
             self.prior_kind, self.prior_params, self.x0vec = cache[key]
             self.prior_kind_host = tuple(int(k) for k in np.asarray(spec[0]).ravel())
 
+    MAX_MODELS = 16          # abc_models_propose
+    MAX_MODEL_DIM = 64
+
+    def _init_models(self, abc):
+        """The batched form of a generation over M > 1 models (staged rounds,
+        one rank, MultivariateNormalTransition): ``models`` holds the
+        per-model prior specs, parameter names, transitions, the scan of the
+        model proposal masses q~ and log(pi(m) / model_factor(m)); anything
+        outside that is named in ``why_not`` and runs the per-candidate
+        loop."""
+        from .sampler import distributed as dd
+        t, M = self.t, len(abc.models)
+        prior_t = t <= 0 or self.all_accepted
+        why = []
+        if M > self.MAX_MODELS:
+            why.append(f"more than {self.MAX_MODELS} models")
+        for m, model in enumerate(abc.models):
+            if not isinstance(model, VectorizedModel):
+                why.append(f"model {m} is not a VectorizedModel")
+            elif list(model.sum_stat_keys) != self.sum_stat_keys:
+                why.append(f"model {m} sum_stat_keys differ from x_0 key order")
+        if abc.summary_statistics is not identity:
+            why.append("custom summary_statistics function")
+        if self.nr_samples_per_parameter != 1:
+            why.append("nr_samples_per_parameter != 1")
+        if isinstance(abc.acceptor, StochasticAcceptor):
+            why.append("StochasticAcceptor with several models")
+        elif not isinstance(abc.acceptor, UniformAcceptor) or \
+                abc.acceptor.use_complete_history:
+            why.append("acceptor is not UniformAcceptor(current time)")
+        if self.distance is not None and (
+                not hasattr(self.distance, "device_call")
+                or not getattr(self.distance, "batched_capable", True)):
+            why.append(getattr(self.distance, "batched_why_not", "")
+                       or "distance has no device kernel")
+        if dd.world()[1] > 1:
+            why.append("several ranks with several models")
+        # per-model prior specs, computed once per run() like the single one
+        cached = abc.__dict__.get("_prior_spec_cache")
+        if cached is None or cached[0] is not abc.parameter_priors:
+            specs = [pr.device_spec() if hasattr(pr, "device_spec") else None
+                     for pr in abc.parameter_priors]
+            hosts = [pr.host_components() if sp is not None else []
+                     for pr, sp in zip(abc.parameter_priors, specs)]
+            cached = (abc.parameter_priors, specs, hosts)
+            abc.__dict__["_prior_spec_cache"] = cached
+        specs, hosts = cached[1], cached[2]
+        names = [pr.get_parameter_names() for pr in abc.parameter_priors]
+        for m in range(M):
+            if specs[m] is None:
+                why.append(f"prior of model {m} has a component without a "
+                           "batched form")
+            elif hosts[m]:
+                why.append(f"prior of model {m} has a host-scipy component "
+                           "(several models)")
+            if not 1 <= len(names[m]) <= self.MAX_MODEL_DIM:
+                why.append(f"model {m} has {len(names[m])} parameters (1 .. "
+                           f"{self.MAX_MODEL_DIM})")
+        self.host_prior = []
+        if why:
+            # (the closure's own model steps run as they always did)
+            self.why_not = "; ".join(why)
+            self.batched_capable = False
+            return
+        prior_pmf = np.array([float(abc.model_prior.pmf(m)) for m in range(M)])
+        if prior_t:
+            masses, log_scale = prior_pmf, np.zeros(M)
+            transitions = [None] * M
+        else:
+            probs = abc.history.model_probabilities_dict(t - 1)
+            masses, factor = model_proposal_masses(
+                probs, abc.model_perturbation_kernel, prior_pmf)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                log_scale = np.log(prior_pmf) - np.log(factor)
+            transitions = list(abc.transitions)
+            for m in range(M):
+                if masses[m] <= 0:
+                    transitions[m] = None
+                    continue
+                tr = transitions[m]
+                if not isinstance(tr, MultivariateNormalTransition) or \
+                        getattr(tr, "_dev_L", None) is None or \
+                        getattr(tr, "_dev_X", None) is None:
+                    why.append(f"transition of model {m} is not a fitted "
+                               "MultivariateNormalTransition")
+        if not masses.sum() > 0:
+            why.append("no model with positive proposal mass")
+        self.why_not = "; ".join(why)
+        self.batched_capable = not why
+        if not self.batched_capable:
+            return
+        x0 = np.array([abc.x_0[k] for k in self.sum_stat_keys], dtype=np.float64)
+        key = ("models", tuple((np.asarray(sp[0]).tobytes(), np.asarray(sp[1]).tobytes())
+                               for sp in specs), x0.tobytes())
+        cache = abc.__dict__.setdefault("_device_consts", {})
+        if key not in cache:
+            dev = gpu.require_device()
+            cache.clear()
+            cache[key] = ([gpu.as_dev(sp[0], dtype=gpu.torch.int32, device=dev)
+                           for sp in specs],
+                          [gpu.as_dev(sp[1], device=dev) for sp in specs],
+                          gpu.as_dev(x0, device=dev))
+        kinds, params, self.x0vec = cache[key]
+        self.models = dict(
+            M=M, param_names=names, d=[len(n) for n in names], prior_kind=kinds,
+            prior_params=params, transitions=transitions, vmodels=list(abc.models),
+            model_cdf=np.cumsum(masses), masses=masses, log_scale=log_scale)
+
     def __call__(self):
         if self._closure is None:
             if self.all_accepted:
@@ -154,11 +268,31 @@ class GenerationSpec:
         return self._closure()
 
 
+def model_proposal_masses(probs, kernel, prior_pmf):
+    """(q~ [M], model_factor [M]) of a generation t > 0 from the previous
+    generation's model probabilities ``probs`` ({m: p_m}, the alive models),
+    the model perturbation kernel (used through ``pmf(n, m)`` only) and the
+    model prior's pmf [M].
+    model_factor(m) = sum_{m_prev} p_{m_prev} K(m | m_prev) is the model part
+    of the transition density (smc.py:792-795), summed over the alive models
+    as the reference writes it.  q~ is the law of the proposal's model steps
+    (smc.py:641-656: source ~ p, target ~ K(. | source), again while the
+    target is dead; a target of prior mass 0 can never be returned): the same
+    sum for an alive target of positive prior mass, 0 elsewhere."""
+    M = len(prior_pmf)
+    factor = np.array([sum(p * kernel.pmf(m, int(mp)) for mp, p in probs.items())
+                       for m in range(M)], dtype=np.float64)
+    ok = np.array([probs.get(m, 0.0) > 0 and prior_pmf[m] > 0 for m in range(M)])
+    return np.where(ok, factor, 0.0), factor
+
+
 class ModelPerturbationKernel:
     """Model jump of multi-model runs (the role of
     random_variables.py:455-538 at smc.py:641-649): from model m stay with
     probability p_stay, else move to one of the other models uniformly.
-    Not on the batched path (single-model generations only)."""
+    The batched path uses it through ``pmf`` only: the sampler draws the
+    target model from sum_m p_m K(. | m) on the device
+    (model_proposal_masses, abc_models_propose)."""
 
     def __init__(self, nr_of_models: int, probability_to_stay=None):
         self.nr_of_models = int(nr_of_models)
@@ -346,10 +480,13 @@ class ABCSMC:
     def _update_population_distances(self, population, t):
         """population.update_distances (population.py:147-162), batched on
         the device for columnar populations."""
-        if population.columns is not None and hasattr(
+        cols = population.columns
+        if cols is None and getattr(population, "model_columns", None):
+            cols = next(iter(population.model_columns.values()))
+        if cols is not None and hasattr(
                 self.distance_function, "device_call") and not getattr(
                 self.distance_function, "batched_why_not", ""):
-            x0vec = gpu.as_dev(np.array([self.x_0[k] for k in population.columns.sum_stat_keys],
+            x0vec = gpu.as_dev(np.array([self.x_0[k] for k in cols.sum_stat_keys],
                                         dtype=np.float64))
             population.update_distances_device(self.distance_function, x0vec, t)
         else:
@@ -631,6 +768,9 @@ class ABCSMC:
 
     @staticmethod
     def _ess_async(population):
+        if getattr(population, "model_columns", None) is not None:
+            ess = population._ess       # host arithmetic on M numbers
+            return lambda: ess
         if population.columns is not None:
             fut = gpu.HostFuture(population._stats[1:2])
             return lambda: float(fut.get()[0])
@@ -640,6 +780,8 @@ class ABCSMC:
     @staticmethod
     def _ess(population):
         """effective_sample_size of the normalised weights (smc.py:930)."""
+        if getattr(population, "model_columns", None) is not None:
+            return population._ess
         if population.columns is not None:
             return float(population._stats[1].item())
         return effective_sample_size(population.get_weighted_distances()['w'])
@@ -745,8 +887,11 @@ class ABCSMC:
         place (no DataFrame round trip)."""
         if t == 0:
             return
+        several = len(self.models) > 1
         for m in self.history.alive_models(t - 1):
-            cols = self.history.get_population_device(t - 1)
+            # (several models: model m's own segment of the population)
+            cols = (self.history.get_population_device(t - 1, m) if several
+                    else self.history.get_population_device(t - 1))
             tr = self.transitions[m]
             if cols is not None and hasattr(tr, "fit_device"):
                 tr.fit_device(cols.theta, cols.weights, cols.param_names)

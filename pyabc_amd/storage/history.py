@@ -68,7 +68,30 @@ class _Gen:
         if self.host is not None:
             return self.host
         pop = self.population
-        if pop.columns is not None:
+        mcols = getattr(pop, "model_columns", None)
+        if mcols is not None:
+            # several models: the rows model by model; parameter columns are
+            # the union of the models' names (NaN where a model has none)
+            names = sorted({n for c in mcols.values() for n in c.param_names})
+            n = len(pop)
+            theta = np.full((n, len(names)), np.nan)
+            off = 0
+            for c in mcols.values():
+                col = [names.index(k) for k in c.param_names]
+                theta[off:off + len(c), col] = c.theta.cpu().numpy()
+                off += len(c)
+            first = next(iter(mcols.values()))
+            cat = lambda f: np.concatenate([f(c).cpu().numpy() for c in mcols.values()])
+            self.host = dict(theta=theta, w=cat(lambda c: c.weights),
+                             distance=cat(lambda c: c.distances),
+                             sum_stats=cat(lambda c: c.sum_stats),
+                             names=names, keys=list(first.sum_stat_keys),
+                             m=np.concatenate([np.full(len(c), m, dtype=int)
+                                               for m, c in mcols.items()]),
+                             model_names_of={m: list(c.param_names)
+                                             for m, c in mcols.items()},
+                             model_probabilities=dict(pop.get_model_probabilities()))
+        elif pop.columns is not None:
             c = pop.columns
             self.host = dict(theta=c.theta.cpu().numpy(), w=c.weights.cpu().numpy(),
                              distance=c.distances.cpu().numpy(),
@@ -95,14 +118,19 @@ class _Gen:
         pop = self.population
         if self.host is None and pop is not None and pop.columns is not None:
             return {pop.columns.m: 1.0}      # single-model columnar population
+        if self.host is None and getattr(pop, "model_columns", None) is not None:
+            return dict(pop.get_model_probabilities())
         return self.to_host().get("model_probabilities") or {0: 1.0}
 
     def device_bytes(self):
         pop = self.population
-        if pop is None or pop.columns is None:
+        if pop is not None and getattr(pop, "model_columns", None) is not None:
+            cols = list(pop.model_columns.values())
+        elif pop is None or pop.columns is None:
             return 0
-        c = pop.columns
-        return sum(t.numel() * t.element_size()
+        else:
+            cols = [pop.columns]
+        return sum(t.numel() * t.element_size() for c in cols
                    for t in (c.theta, c.weights, c.distances, c.sum_stats)
                    if t is not None)
 
@@ -262,11 +290,17 @@ class History:
             return g.population
         return _population_from_host(g.to_host())
 
-    def get_population_device(self, t=None):
+    def get_population_device(self, t=None, m=None):
+        """Device columns of generation t: the single-model form, or with m
+        the columns of model m of a population over several models (None
+        when that form is not resident)."""
         t = self.max_t if t is None else t
         g = self._gens.get(t)
         if g is None or g.population is None:
             return None
+        mcols = getattr(g.population, "model_columns", None)
+        if m is not None and mcols is not None:
+            return mcols.get(int(m))
         return g.population.columns
 
     def get_distribution(self, m=0, t=None):
@@ -275,7 +309,12 @@ class History:
         t = self.max_t if t is None else t
         h = self._gens[t].to_host()
         sel = h["m"] == m
-        df = pd.DataFrame(h["theta"][sel], columns=h["names"])
+        own = h.get("model_names_of", {}).get(m)
+        if own is not None:      # several models: the model's own parameters
+            df = pd.DataFrame(h["theta"][sel][:, [h["names"].index(k) for k in own]],
+                              columns=own)
+        else:
+            df = pd.DataFrame(h["theta"][sel], columns=h["names"])
         w = h["w"][sel]
         w = w / w.sum() if w.size else w
         return df, w
