@@ -302,7 +302,9 @@ int abc_simulate_linear_gaussian(const double* theta, int64_t B, int d, int S,
 
 /* ---- PNormDistance.__call__ (pyabc/distance/distance.py:79-105) ----------
  * d[b] = (sum_k |wf[k] (x[b,k] - x0[k])|^p)^(1/p); p = +inf -> max.
- * wf = weights * factors, in x_0 key order. */
+ * wf = weights * factors, in x_0 key order.  A row with a NaN term (NaN
+ * in x, x0 or wf, inf - inf, 0 inf) is NaN for every p, the max of p = +inf
+ * included, and so is never accepted. */
 int abc_pnorm(const double* x, int64_t B, int S, const double* x0,
               const double* wf, double p, double* d, void* stream);
 

@@ -9,7 +9,7 @@
 // calls pnorm_row itself; the wide path repeats pnorm_wave_rows' operations
 // in its order (lane-strided partials over k, then the wave tree, then
 // pnorm_finish) for up to AGG_TG terms per loaded value, through pterm,
-// wave_sum / wave_max and pnorm_finish<0> of abc_candidate.h.  Contraction is
+// wave_sum / wave_pnorm_max and pnorm_finish<0> of abc_candidate.h.  Contraction is
 // off, so no kernel fuses differently from another.
 //
 // The wide path keeps pnorm_wave_rows' PNORM_ROWS rows in flight per wave and
@@ -128,7 +128,7 @@ __device__ __forceinline__ void agg_wave_rows(const double* x, int64_t b0, int64
           for (int r = 0; r < PNORM_ROWS; ++r) a[r] = fabs(wk[t] * v[r]);
           if (inf[t]) {
 #pragma unroll
-            for (int r = 0; r < PNORM_ROWS; ++r) s[r][t] = fmax(s[r][t], a[r]);
+            for (int r = 0; r < PNORM_ROWS; ++r) s[r][t] = pnorm_max(s[r][t], a[r]);
           } else if (pt[t] == 1.0) {
 #pragma unroll
             for (int r = 0; r < PNORM_ROWS; ++r) s[r][t] = s[r][t] + a[r];
@@ -147,7 +147,7 @@ __device__ __forceinline__ void agg_wave_rows(const double* x, int64_t b0, int64
       if (t < nt) {
 #pragma unroll
         for (int r = 0; r < PNORM_ROWS; ++r) {
-          const double w = inf[t] ? wave_max(s[r][t]) : wave_sum(s[r][t]);
+          const double w = inf[t] ? wave_pnorm_max(s[r][t]) : wave_sum(s[r][t]);
           if (lane == 0 && b0 + r < B) {
             const double tv = agg_finish<SIMPLE>(w, pt[t]);
             term(r, k0 + t, tv);

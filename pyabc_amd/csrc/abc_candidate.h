@@ -686,6 +686,21 @@ __device__ __forceinline__ double pterm(double v, double p) {
 #pragma clang fp contract(off)
   return (p == 1.0) ? v : (p == 2.0 ? v * v : pow(v, p));
 }
+// The max of the p = inf norm.  fmax drops a NaN (fmax(s, NaN) = s), so a row
+// with a NaN statistic would get a finite distance and could be accepted,
+// while every finite p sums it to NaN and rejects it.  This one keeps it: a
+// NaN v is taken, and a NaN s stays (NaN < v is false) -- a NaN statistic is
+// never accepted, for any p, wherever it sits in the row.  s and v are
+// |.| or +0: for non-NaN arguments the result is fmax's, bit for bit.
+__device__ __forceinline__ double pnorm_max(double s, double v) {
+  return (v > s || v != v) ? v : s;
+}
+// wave_max (abc_common.h) with pnorm_max: NaN in any lane -> NaN in all
+__device__ __forceinline__ double wave_pnorm_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = pnorm_max(v, __shfl_xor(v, o, 64));
+  return v;
+}
 // running p-norm state s (sum of |.|^p, or max for p = inf); order = k order.
 // PK = 2: p == 2 known at compile time (the same operations as the runtime
 // p == 2 branch, so the same bits); PK = 0: any p.  A kernel that can meet a
@@ -695,7 +710,7 @@ template <int PK = 0>
 __device__ __forceinline__ double pnorm_acc(double s, double v, double p) {
 #pragma clang fp contract(off)
   if constexpr (PK == 2) return s + v * v;
-  return isinf(p) ? fmax(s, v) : s + pterm(v, p);
+  return isinf(p) ? pnorm_max(s, v) : s + pterm(v, p);
 }
 template <int PK = 0>
 __device__ __forceinline__ double pnorm_finish(double s, double p) {
@@ -714,7 +729,7 @@ __device__ __forceinline__ double pnorm_row(const double* xr, int S, const doubl
 #pragma clang fp contract(off)
   double s = 0.0;
   if (isinf(p)) {
-    for (int k = 0; k < S; ++k) s = fmax(s, fabs(wf[k] * (xr[k] - x0[k])));
+    for (int k = 0; k < S; ++k) s = pnorm_max(s, fabs(wf[k] * (xr[k] - x0[k])));
     return pnorm_finish<0>(s, p);
   }
   for (int k = 0; k < S; ++k) s += pterm(fabs(wf[k] * (xr[k] - x0[k])), p);
@@ -745,12 +760,12 @@ __device__ __forceinline__ void pnorm_wave_rows(const double* x, int64_t b0, int
 #pragma unroll
     for (int r = 0; r < PNORM_ROWS; ++r) {
       const double a = fabs(wk * (v[r] - ck));
-      s[r] = inf ? fmax(s[r], a) : s[r] + pterm(a, p);
+      s[r] = inf ? pnorm_max(s[r], a) : s[r] + pterm(a, p);
     }
   }
 #pragma unroll
   for (int r = 0; r < PNORM_ROWS; ++r) {
-    const double t = inf ? wave_max(s[r]) : wave_sum(s[r]);
+    const double t = inf ? wave_pnorm_max(s[r]) : wave_sum(s[r]);
     if (lane == 0 && b0 + r < B) emit(r, pnorm_finish<0>(t, p));
   }
 }

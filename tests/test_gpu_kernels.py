@@ -451,18 +451,31 @@ def test_local_logpdf_mfma_vs_oracle(dev, d, N, M, offset):
 
 
 def test_pnorm_golden(dev):
+    """The kernel within the derived bound of the exact distance of the golden
+    inputs (tests/test_gpu_distance_chain.py derives it), and the reference's
+    own float64 value, which sits within that bound too, within twice it."""
+    import distance_chain_ref as dref
+    from oracle import distance_exact as dx
     from pyabc_amd import gpu
     gg = g("pnorm.npz")
     for c in sorted({k.split("__")[0] for k in gg.files}):
         wf = gg[c + "__w"] * gg[c + "__f"]
-        dd = gpu.pnorm(T(gg[c + "__x"]), T(gg[c + "__x0"]), T(wf),
-                       float(gg[c + "__p"])).cpu().numpy()
-        np.testing.assert_allclose(dd, gg[c + "__d"], rtol=1e-12, err_msg=c)
+        x, x0, pv = gg[c + "__x"], gg[c + "__x0"], float(gg[c + "__p"])
+        dd = gpu.pnorm(T(x), T(x0), T(wf), pv).cpu().numpy()
+        r = dx.pnorm_exact(x, x0, wf, pv)
+        bound = dref.bound_u(x.shape[1], pv, r.sum_p)
+        e, ok = dref.rel_err_u(dd, r)
+        assert ok.all() and (np.abs(e) <= bound).all(), c
+        assert (np.abs(dd - gg[c + "__d"]) <= 2 * bound * dref.U * r.d).all(), c
 
 
 @pytest.mark.parametrize("B,S", [(1, 33), (3, 256), (17, 100), (1001, 256), (64, 700)])
 def test_pnorm_wave_rows_vs_oracle(dev, B, S):
-    """Wide-row PNorm (S > 32: several rows per wave, ragged last wave)."""
+    """Wide-row PNorm (S > 32: several rows per wave, ragged last wave)
+    against the exact distance, within the bound derived in
+    tests/test_gpu_distance_chain.py."""
+    import distance_chain_ref as dref
+    from oracle import distance_exact as dx
     from pyabc_amd import gpu
     rng = np.random.default_rng(B * 1000 + S)
     x = rng.standard_normal((B, S)) * 10 ** rng.uniform(-2, 2, S)
@@ -470,8 +483,9 @@ def test_pnorm_wave_rows_vs_oracle(dev, B, S):
     w = rng.uniform(0.1, 2.0, S)
     for p in (1.0, 2.0, 3.0, np.inf):
         dd = gpu.pnorm(T(x), T(x0), T(w), p).cpu().numpy()
-        np.testing.assert_allclose(dd, oracle.pnorm(x, x0, w=w, p=p), rtol=1e-12,
-                                   err_msg=f"p={p}")
+        r = dx.pnorm_exact(x, x0, w, p)
+        e, ok = dref.rel_err_u(dd, r)
+        assert ok.all() and (np.abs(e) <= dref.bound_u(S, p, r.sum_p)).all(), f"p={p}"
 
 
 def test_weighted_quantile_golden(dev):
