@@ -370,11 +370,12 @@ def pnorm(x, x0, wf, pval, out=None):
     return out
 
 
-def pnorm_accept(x, x0, wf, pval, eps, cap, att=None, max_attempts=0):
-    """Accept tail of one staged round (abc_pnorm_accept): the positions of
-    the first `cap` rows of x [B, S] whose p-norm distance to x0 is <= eps
-    (and whose proposal did not give up), and the number accepted [1] int64,
-    without a distance array.  x must be contiguous float64."""
+def _accept_tail(name, x, args, eps, cap, att, max_attempts):
+    """What the accept tails share (abc_pnorm_accept, abc_aggregate_accept,
+    abc_whitened_accept): x [B, S] as contiguous float64, the accept
+    positions of the first `cap` accepted rows and the number accepted [1]
+    int64, the candidates workspace and the call; ``args``: the kernel's own
+    arguments between x0 and eps, x0 first."""
     B, S = x.shape
     if x.dtype != F64 or not x.is_contiguous():
         x = x.to(F64).contiguous()
@@ -383,10 +384,18 @@ def pnorm_accept(x, x0, wf, pval, eps, cap, att=None, max_attempts=0):
     cnt = torch.empty(1, dtype=I64, device=x.device)
     nb = nat.query("abc_candidates_workspace", int(B))
     ws = workspace(nb, "candidates")
-    nat.call("abc_pnorm_accept", p(x), int(B), int(S), p(x0), p(wf), float(pval),
-             float(eps), p(att), int(max_attempts), cap, p(idx), p(cnt), p(ws),
-             ws.numel(), stream_ptr())
+    nat.call(name, p(x) if B else None, int(B), int(S), *args, float(eps), p(att),
+             int(max_attempts), cap, p(idx), p(cnt), p(ws), ws.numel(), stream_ptr())
     return idx, cnt
+
+
+def pnorm_accept(x, x0, wf, pval, eps, cap, att=None, max_attempts=0):
+    """Accept tail of one staged round (abc_pnorm_accept): the positions of
+    the first `cap` rows of x [B, S] whose p-norm distance to x0 is <= eps
+    (and whose proposal did not give up), and the number accepted [1] int64,
+    without a distance array."""
+    return _accept_tail("abc_pnorm_accept", x, (p(x0), p(wf), float(pval)), eps, cap,
+                        att, max_attempts)
 
 
 class TermStack:
@@ -427,50 +436,41 @@ def aggregate_distance(x, x0, stack, out=None, terms=False):
 
 def aggregate_accept(x, x0, stack, eps, cap, att=None, max_attempts=0):
     """pnorm_accept for a TermStack (abc_aggregate_accept)."""
-    B, S = x.shape
-    if x.dtype != F64 or not x.is_contiguous():
-        x = x.to(F64).contiguous()
-    if stack.wf.shape[1] != S:
+    if stack.wf.shape[1] != x.shape[1]:
         raise ValueError(f"aggregate_accept: weights for {stack.wf.shape[1]} "
-                         f"statistics, rows of {S}")
-    cap = int(min(max(cap, 0), B))
-    idx = torch.empty(max(cap, 1), dtype=I64, device=x.device)
-    cnt = torch.empty(1, dtype=I64, device=x.device)
-    nb = nat.query("abc_candidates_workspace", int(B))
-    ws = workspace(nb, "candidates")
-    nat.call("abc_aggregate_accept", p(x), int(B), int(S), p(x0), *stack.args(),
-             float(eps), p(att), int(max_attempts), cap, p(idx), p(cnt), p(ws),
-             ws.numel(), stream_ptr())
-    return idx, cnt
+                         f"statistics, rows of {x.shape[1]}")
+    return _accept_tail("abc_aggregate_accept", x, (p(x0), *stack.args()), eps, cap,
+                        att, max_attempts)
 
 
-class PNormTail:
-    """The staged round's accept tail for one p-norm: the round's accept
-    positions without a distance array, then the kept rows' distances."""
+class AcceptTail:
+    """The staged round's accept tail of one distance: ``accept`` gives the
+    round's accept positions without a distance array, ``distances`` the kept
+    rows' distances afterwards (the same per-row arithmetic).  ``accept_fn``
+    and ``distance_fn`` are names of this module's functions, looked up at
+    call time; ``args`` follow (x, x0) in both."""
 
-    def __init__(self, wf, pval):
-        self.wf, self.pval = wf, pval
+    def __init__(self, accept_fn, distance_fn, *args):
+        self.accept_fn, self.distance_fn, self.args = accept_fn, distance_fn, args
 
     def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
-        return pnorm_accept(x, x0, self.wf, self.pval, eps, cap, att=att,
-                            max_attempts=max_attempts)
+        return globals()[self.accept_fn](x, x0, *self.args, eps, cap, att=att,
+                                         max_attempts=max_attempts)
 
     def distances(self, rows, x0):
-        return pnorm(rows, x0, self.wf, self.pval)
+        return globals()[self.distance_fn](rows, x0, *self.args)
 
 
-class AggregateTail:
-    """PNormTail for a TermStack."""
+def PNormTail(wf, pval):
+    return AcceptTail("pnorm_accept", "pnorm", wf, pval)
 
-    def __init__(self, stack):
-        self.stack = stack
 
-    def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
-        return aggregate_accept(x, x0, self.stack, eps, cap, att=att,
-                                max_attempts=max_attempts)
+def AggregateTail(stack):
+    return AcceptTail("aggregate_accept", "aggregate_distance", stack)
 
-    def distances(self, rows, x0):
-        return aggregate_distance(rows, x0, self.stack)
+
+def WhitenedTail(W):
+    return AcceptTail("whitened_accept", "whitened_norm", W)
 
 
 def _whiten_check(x, W):
@@ -496,29 +496,8 @@ def whitened_norm(x, x0, W, out=None):
 def whitened_accept(x, x0, W, eps, cap, att=None, max_attempts=0):
     """pnorm_accept for the whitened norm (abc_whitened_accept)."""
     x, B, S = _whiten_check(x, W)
-    cap = int(min(max(cap, 0), B))
-    idx = torch.empty(max(cap, 1), dtype=I64, device=x.device)
-    cnt = torch.empty(1, dtype=I64, device=x.device)
-    nb = nat.query("abc_candidates_workspace", B)
-    ws = workspace(nb, "candidates")
-    nat.call("abc_whitened_accept", p(x) if B else None, B, S, p(x0), p(W), float(eps),
-             p(att), int(max_attempts), cap, p(idx), p(cnt), p(ws), ws.numel(),
-             stream_ptr())
-    return idx, cnt
-
-
-class WhitenedTail:
-    """PNormTail for the whitened norm of a device matrix W [S, S]."""
-
-    def __init__(self, W):
-        self.W = W
-
-    def accept(self, x, x0, eps, cap, att=None, max_attempts=0):
-        return whitened_accept(x, x0, self.W, eps, cap, att=att,
-                               max_attempts=max_attempts)
-
-    def distances(self, rows, x0):
-        return whitened_norm(rows, x0, self.W)
+    return _accept_tail("abc_whitened_accept", x, (p(x0), p(W)), eps, cap, att,
+                        max_attempts)
 
 
 def prior_uniforms(att, k, seed, generation, idx0, B=None):

@@ -281,12 +281,133 @@ class _RoundLedger:
         return out
 
 
+class _OneModelSource:
+    """Candidate source of a one-model generation: proposals of the cached
+    proposal-only CandidateRound (gpu.propose / propose_device where it has
+    none), the model's own simulate_batch."""
+
+    def __init__(self, sampler, spec, seed, gen, dev, all_accepted):
+        self.sampler, self.spec, self.dev = sampler, spec, dev
+        self.seed, self.gen, self.all_accepted = seed, gen, all_accepted
+        self.d = len(spec.param_names)         # the round size's dimension
+        # t = 0: the host-scipy leg draws its coordinates as ppf of the
+        # candidates' own prior-stream uniforms
+        self.host_draw = (getattr(spec, "host_prior", None)
+                          if spec.transition is None else None)
+
+    def propose(self, lo, B):
+        """(the candidates' columns, att)."""
+        theta, lp, anc, att = self.sampler._propose(self.spec, B, self.seed,
+                                                    self.gen, lo, self.d)
+        if self.host_draw:
+            host_prior_draw(theta, att, self.host_draw, self.seed, self.gen, lo)
+        return dict(theta=theta, lp=lp, anc=anc), att
+
+    def simulate(self, cand, lo):
+        return self.spec.model.simulate_batch(cand["theta"], self.seed, self.gen, lo)
+
+    def kept_columns(self, cand):
+        """The candidates' columns that ride with a kept row."""
+        return {k: v for k, v in cand.items() if v is not None}
+
+    def complete(self, got, att, unfiltered):
+        """The prior log-density of the kept rows, where the proposal left
+        it out: the bits the proposal kernel would have written (same device
+        function)."""
+        if "lp" in got:
+            return
+        spec = self.spec
+        got["lp"] = gpu.prior_logpdf(got["theta"], spec.prior_kind, spec.prior_params)
+        if unfiltered and att is not None:
+            # rows 0..k-1 are kept unfiltered, including proposals that
+            # exhausted max_attempts: their last draw's density is not the
+            # proposal's, and the proposal kernel would have written -inf
+            # (weight 0)
+            gpu.mask_gave_up(got["lp"], att[:got["lp"].numel()],
+                             self.sampler.max_attempts, -np.inf)
+
+    def assemble(self, kept, led):
+        """(population columns, the ranks' cutoff positions or None, the
+        source's own last_stats keys)."""
+        cols, gathered = self.sampler._assemble(self.spec, kept, self.dev, self.d,
+                                                self.all_accepted, led)
+        return cols, gathered, {}
+
+    def sample(self, cols, recorded, record, ok, records):
+        if recorded is None and cols is not None:
+            recorded = cols.sum_stats
+        return ColumnarSample(cols, recorded, self.spec.sum_stat_keys, record, ok,
+                              records=records)
+
+
+class _ModelsSource:
+    """Candidate source of a generation over M > 1 models (one rank).  A
+    round proposes (model, theta) per candidate (abc_models_propose: the
+    reference's model steps and whole-attempt re-draw, smc.py:610-662) and
+    simulates every row under its model; the kept rows are split by model at
+    the end and weighted per model (smc.py:754-811):
+    w = pi(m) prior_m(theta) / (model_factor(m) T_m(theta))."""
+
+    def __init__(self, sampler, spec, seed, gen, dev, all_accepted):
+        self.sampler, self.spec, self.dev = sampler, spec, dev
+        self.seed, self.gen, self.all_accepted = seed, gen, all_accepted
+        ms = self.ms = spec.models
+        self.d = max(ms["d"])
+        descs = []
+        for m in range(ms["M"]):
+            desc = dict(d=ms["d"][m], prior_kind=ms["prior_kind"][m],
+                        prior_params=ms["prior_params"][m])
+            tr = ms["transitions"][m]
+            if tr is not None:
+                desc.update(X=tr._dev_X, cdf=tr._dev_cdf, guide=tr._dev_guide, L=tr._dev_L)
+            descs.append(desc)
+        self.mset = gpu.ModelSet(descs, ms["model_cdf"], seed, gen, sampler.max_attempts)
+        sims = [mod.fused_simulator(dev) if hasattr(mod, "fused_simulator") else None
+                for mod in ms["vmodels"]]
+        self.tables = None
+        if all(sim is not None for sim in sims):
+            self.tables = tuple(gpu.torch.stack([sim[k] for sim in sims]).contiguous()
+                                for k in range(3))
+
+    def propose(self, lo, B):
+        model, theta, anc, att = self.mset.propose(lo, B)
+        return dict(theta=theta, anc=anc, model=model), att
+
+    def simulate(self, cand, lo):
+        if self.tables is not None:
+            return gpu.models_simulate_linear_gaussian(
+                cand["theta"], cand["model"], *self.tables, self.seed, self.gen, lo)
+        return self.sampler._simulate_by_model(
+            self.ms, cand["model"], cand["theta"], self.seed, self.gen, lo,
+            len(self.spec.sum_stat_keys))
+
+    def kept_columns(self, cand):
+        # model and ancestor travel as 8-byte columns of the one gather
+        return dict(cand, model=cand["model"].to(gpu.I64))
+
+    def complete(self, got, att, unfiltered):
+        pass        # the prior density is taken per model (_assemble_models)
+
+    def assemble(self, kept, led):
+        cols = self.sampler._assemble_models(self.spec, kept, self.dev,
+                                             self.all_accepted)
+        return cols, None, dict(models=self.ms["M"],
+                                accepted_per_model={m: len(c) for m, c in cols.items()})
+
+    def sample(self, cols, recorded, record, ok, records):
+        if recorded is None and cols:
+            recorded = gpu.torch.cat([c.sum_stats for c in cols.values()])
+        return ModelsSample(cols, recorded, self.spec.sum_stat_keys, record, ok)
+
+
 class BatchedGPUSampler(Sampler):
     """Batched, device-resident sampler (nr_samples_per_param 1): fused or
-    staged rounds for one model, staged multi-model rounds for 2 to 16 models
-    (_sample_models).  Closures outside that (a plain ``simulate_one``, a
-    scalar model, ...) run the reference's per-candidate loop instead
-    (_sample_per_candidate).
+    staged rounds for one model, staged rounds for 2 to 16 models.  The
+    staged rounds are one loop over a candidate source (_OneModelSource,
+    _ModelsSource), which proposes and simulates a round's candidates and
+    turns the kept rows into the sample.  Closures outside that (a plain
+    ``simulate_one``, a scalar model, ...) run the reference's per-candidate
+    loop instead (_sample_per_candidate).
 
     Parameters
     ----------
@@ -405,13 +526,16 @@ class BatchedGPUSampler(Sampler):
         gen = spec.t & 0xFFFFFFFF
         record = self.sample_factory.record_rejected
         if getattr(spec, "models", None) is not None:
-            return self._sample_models(n, spec, max_eval, record, dev, seed, gen,
-                                       all_accepted)
-        d = len(spec.param_names)
-        fr = None if all_accepted else self._fused_round(spec, seed, gen, dev)
-        if fr is not None:
-            return self._sample_fused(n, fr, spec, max_eval, record, dev, rank, ws)
+            src = _ModelsSource(self, spec, seed, gen, dev, all_accepted)
+        else:
+            src = _OneModelSource(self, spec, seed, gen, dev, all_accepted)
+            fr = None if all_accepted else self._fused_round(spec, seed, gen, dev)
+            if fr is not None:
+                return self._sample_fused(n, fr, spec, src, max_eval, record, dev,
+                                          rank, ws)
 
+        # staged rounds, the same loop for one model and for several: only
+        # the candidate source differs
         S = len(spec.sum_stat_keys)
         kept = {k: [] for k in self._KEPT}       # kept rows' columns per round
         rec_x = []
@@ -419,8 +543,8 @@ class BatchedGPUSampler(Sampler):
         unfiltered = all_accepted or spec.distance is None
         stochastic = getattr(spec, "stochastic", None) is not None and not all_accepted
         # the accept tail (abc_pnorm_accept): a p-norm distance and the
-        # uniform acceptor decided in one pass over the user simulator's
-        # rows, no distance array; the kept rows' distances afterwards
+        # uniform acceptor decided in one pass over the simulator's rows, no
+        # distance array; the kept rows' distances afterwards
         tail = None
         if not (stochastic or unfiltered) and self.accept_tail:
             tail = self._accept_tail(spec, dev)
@@ -431,198 +555,101 @@ class BatchedGPUSampler(Sampler):
         while led.need > 0:
             if self.check_max_eval and led.n_eval >= max_eval:
                 break
-            B = self._limit_to_max_eval(self._round_size(led.need, ws, d, S),
+            B = self._limit_to_max_eval(self._round_size(led.need, ws, src.d, S),
                                         max_eval, led.n_eval, ws)
             kk = min(led.need, B)
             lo, _ = dd.rank_range(led.base, B, rank)
-            theta, lp, anc, att = self._propose(spec, B, seed, gen, lo, d)
-            if spec.transition is None and getattr(spec, "host_prior", None):
-                # t = 0: the host-scipy leg draws its coordinates as ppf of
-                # the candidates' own prior-stream uniforms
-                host_prior_draw(theta, att, spec.host_prior, seed, gen, lo)
-            x = spec.model.simulate_batch(theta, seed, gen, lo)
-            dist = None
-            if tail is not None:
-                if x.dtype != gpu.F64 or not x.is_contiguous():
-                    x = x.to(gpu.F64).contiguous()
-                idx, cnt = tail.accept(x, spec.x0vec, spec.eps, kk, att=att,
-                                       max_attempts=self.max_attempts)
-            elif unfiltered:
-                dist = gpu.torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
-                idx = gpu.torch.arange(B, dtype=gpu.I64, device=dev)
-            else:
-                dist = spec.distance.device_call(x, spec.x0vec, spec.t,
-                                                 spec.sum_stat_keys)
-                # a proposal that exhausted max_attempts never enters the
-                # population (the reference loops until the prior density is
-                # positive, smc.py:649-662): its distance becomes NaN (never
-                # <= eps, even at eps = inf); under a StochasticAcceptor the
-                # "distance" is a density, so it becomes the zero-probability
-                # density instead (acceptance 0, weight 0, and a zero
-                # acceptance base in the temperature records)
-                if att is not None:
-                    if stochastic:
-                        gpu.mask_gave_up(dist, att, self.max_attempts,
-                                         -np.inf if spec.stochastic[2] else 0.0)
-                    else:
-                        gpu.mask_gave_up(dist, att, self.max_attempts)
-                if stochastic:
-                    key, accw = gpu.stochastic_accept(dist, *spec.stochastic,
-                                                      seed, gen, lo)
-                    if att is not None:
-                        # key +inf: never accepted, and marks the row for
-                        # ABCSMC._device_records, which leaves it out
-                        gpu.mask_gave_up(key, att, self.max_attempts, np.inf)
-                    idx, cnt = gpu.accept_compact(key, 0.0)
-                else:
-                    idx, cnt = gpu.accept_compact(dist, spec.eps)
-            if unfiltered:
-                # idx is arange(B): the k-th kept is candidate k - 1, no read
-                cnt_local, pos = B, kk - 1
-            elif ws == 1:
-                # one read: the count and the index of the n-th accepted
-                # (meaningful only when this round completes the sample)
-                nth = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
-                cnt_local, pos = gpu.torch.cat([cnt.view(1), nth]).cpu().tolist()
-            else:
-                cnt_local, pos = cnt, None    # gathered on the device, one host read
+            cand, att = src.propose(lo, B)
+            x = src.simulate(cand, lo)
+            if x.dtype != gpu.F64 or not x.is_contiguous():
+                # the kept-row gather moves 8-byte elements: every branch
+                # below takes the simulator's rows as contiguous float64
+                x = x.to(gpu.F64).contiguous()
+            idx, cnt, dist, key, accw = self._accept(
+                spec, x, att, kk, tail, unfiltered, stochastic, seed, gen, lo)
+            cnt_local, pos = self._read_count(idx, cnt, kk, B, ws, unfiltered)
             counts = dd.allgather_counts(cnt_local, dev)
             k_mine, rec_rows = led.settle(counts, B, idx, pos, record)
             if k_mine:
-                sel = idx[:k_mine]
-                lp_cols = [lp] if lp is not None else []
+                cols = dict(src.kept_columns(cand), x=x)
+                if dist is not None:
+                    cols["dist"] = dist
+                if stochastic:
+                    cols["w"] = accw
+                got = dict(zip(cols, gpu.gather_rows_batch(list(cols.values()),
+                                                           idx[:k_mine])))   # one launch
                 if dist is None:
                     # the tail kept no distances: the kept rows' ones, the
                     # same per-row arithmetic (abc_pnorm / abc_aggregate_distance)
-                    cols = [theta] + lp_cols + [x] + ([anc] if anc is not None else [])
-                    got = gpu.gather_rows_batch(cols, sel)
-                    if lp is None:
-                        got.insert(1, None)
-                    got.insert(2, tail.distances(got[2], spec.x0vec))
-                else:
-                    cols = [theta] + lp_cols + [dist, x] + \
-                        ([anc] if anc is not None else []) + ([accw] if stochastic else [])
-                    got = gpu.gather_rows_batch(cols, sel)   # one launch
-                    if lp is None:
-                        got.insert(1, None)
-                if got[1] is None:
-                    # kept rows only: the bits the proposal kernel would have
-                    # written (same device function)
-                    got[1] = gpu.prior_logpdf(got[0], spec.prior_kind, spec.prior_params)
-                    if unfiltered and att is not None:
-                        # this branch keeps rows 0..k-1 unfiltered, including
-                        # proposals that exhausted max_attempts: their last
-                        # draw's density is not the proposal's, and the
-                        # proposal kernel would have written -inf (weight 0)
-                        gpu.mask_gave_up(got[1], att[:k_mine], self.max_attempts, -np.inf)
-                for k, v in zip(("theta", "lp", "dist", "x"), got):
+                    got["dist"] = tail.distances(got["x"], spec.x0vec)
+                src.complete(got, att, unfiltered)
+                for k, v in got.items():
                     kept[k].append(v)
-                if anc is not None:
-                    kept["anc"].append(got[4])
-                if stochastic:
-                    kept["w"].append(got[-1])
             if record:
                 # a pending multi-rank cut keeps the whole round's rows,
                 # trimmed once the cutoff position is known (_finish)
                 rr = B if rec_rows is None else rec_rows
                 rec_x.append(x[:rr].clone() if rr < B // 2 else x[:rr])
                 if rec_extra is not None:
-                    rec_extra.append((theta[:rr], dist[:rr], key[:rr],
+                    anc = cand["anc"]
+                    rec_extra.append((cand["theta"][:rr], dist[:rr], key[:rr],
                                       None if anc is None else anc[:rr]))
             self._acc_rate = max(int(counts.sum()) / float(ws * B), 1e-6)
-        return self._finish(spec, led, kept, rec_x if record else None, rec_extra,
-                            dev, d, all_accepted)
+        return self._finish(led, src, kept, rec_x if record else None, rec_extra, dev)
 
-    # ---- several models --------------------------------------------------
-    def _sample_models(self, n, spec, max_eval, record, dev, seed, gen, all_accepted):
-        """sample_until_n_accepted over M > 1 models (staged rounds, one
-        rank).  A round proposes (model, theta) per candidate
-        (abc_models_propose: the reference's model steps and whole-attempt
-        re-draw, smc.py:610-662), simulates every row under its model,
-        applies the staged loop's accept step to the statistics and keeps
-        the first n accepted in candidate order; the kept rows are split by
-        model at the end and weighted per model (smc.py:754-811):
-        w = pi(m) prior_m(theta) / (model_factor(m) T_m(theta))."""
-        torch = gpu.torch
-        ms = spec.models
-        M, S, dmax = ms["M"], len(spec.sum_stat_keys), max(ms["d"])
-        descs = []
-        for m in range(M):
-            desc = dict(d=ms["d"][m], prior_kind=ms["prior_kind"][m],
-                        prior_params=ms["prior_params"][m])
-            tr = ms["transitions"][m]
-            if tr is not None:
-                desc.update(X=tr._dev_X, cdf=tr._dev_cdf, guide=tr._dev_guide, L=tr._dev_L)
-            descs.append(desc)
-        mset = gpu.ModelSet(descs, ms["model_cdf"], seed, gen, self.max_attempts)
-        sims = [mod.fused_simulator(dev) if hasattr(mod, "fused_simulator") else None
-                for mod in ms["vmodels"]]
-        tables = None
-        if all(sim is not None for sim in sims):
-            tables = tuple(torch.stack([sim[k] for sim in sims]).contiguous()
-                           for k in range(3))
-        unfiltered = all_accepted or spec.distance is None
-        tail = None
-        if not unfiltered and self.accept_tail:
-            tail = self._accept_tail(spec, dev)
-        led = self._ledger(n, 0, 1, S)
-        kept = {k: [] for k in ("model", "theta", "dist", "x", "anc")}
-        rec_x = []
-        while led.need > 0:
-            if self.check_max_eval and led.n_eval >= max_eval:
-                break
-            B = self._limit_to_max_eval(self._round_size(led.need, 1, dmax, S),
-                                        max_eval, led.n_eval, 1)
-            kk = min(led.need, B)
-            lo = led.base
-            model, theta, anc, att = mset.propose(lo, B)
-            if tables is not None:
-                x = gpu.models_simulate_linear_gaussian(theta, model, *tables, seed, gen, lo)
+    def _accept(self, spec, x, att, kk, tail, unfiltered, stochastic, seed, gen, lo):
+        """The accept step of one staged round over the rows x [B, S]:
+        (idx, cnt, dist, key, accw) -- the accepted positions in candidate
+        order and their number (cnt None when unfiltered: all B), the distance
+        array (None with the tail), and the StochasticAcceptor's acceptance
+        keys and weights (else None)."""
+        B, dev = x.shape[0], x.device
+        dist = cnt = key = accw = None
+        if tail is not None:
+            idx, cnt = tail.accept(x, spec.x0vec, spec.eps, kk, att=att,
+                                   max_attempts=self.max_attempts)
+        elif unfiltered:
+            dist = gpu.torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
+            idx = gpu.torch.arange(B, dtype=gpu.I64, device=dev)
+        else:
+            dist = spec.distance.device_call(x, spec.x0vec, spec.t, spec.sum_stat_keys)
+            # a proposal that exhausted max_attempts never enters the
+            # population (the reference loops until the prior density is
+            # positive, smc.py:649-662): its distance becomes NaN (never
+            # <= eps, even at eps = inf); under a StochasticAcceptor the
+            # "distance" is a density, so it becomes the zero-probability
+            # density instead (acceptance 0, weight 0, and a zero
+            # acceptance base in the temperature records)
+            if att is not None:
+                if stochastic:
+                    gpu.mask_gave_up(dist, att, self.max_attempts,
+                                     -np.inf if spec.stochastic[2] else 0.0)
+                else:
+                    gpu.mask_gave_up(dist, att, self.max_attempts)
+            if stochastic:
+                key, accw = gpu.stochastic_accept(dist, *spec.stochastic, seed, gen, lo)
+                if att is not None:
+                    # key +inf: never accepted, and marks the row for
+                    # ABCSMC._device_records, which leaves it out
+                    gpu.mask_gave_up(key, att, self.max_attempts, np.inf)
+                idx, cnt = gpu.accept_compact(key, 0.0)
             else:
-                x = self._simulate_by_model(ms, model, theta, seed, gen, lo, S)
-            dist = None
-            if tail is not None:
-                idx, cnt = tail.accept(x, spec.x0vec, spec.eps, kk, att=att,
-                                       max_attempts=self.max_attempts)
-            elif unfiltered:
-                dist = torch.full((B,), np.inf, dtype=gpu.F64, device=dev)
-                idx = torch.arange(B, dtype=gpu.I64, device=dev)
-            else:
-                dist = spec.distance.device_call(x, spec.x0vec, spec.t, spec.sum_stat_keys)
-                gpu.mask_gave_up(dist, att, self.max_attempts)
                 idx, cnt = gpu.accept_compact(dist, spec.eps)
-            if unfiltered:
-                cnt_local, pos = B, kk - 1
-            else:
-                nth = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
-                cnt_local, pos = torch.cat([cnt.view(1), nth]).cpu().tolist()
-            counts = dd.allgather_counts(cnt_local, dev)
-            k_mine, rec_rows = led.settle(counts, B, idx, pos, record)
-            if k_mine:
-                # model and ancestor travel as 8-byte columns of one gather
-                cols = [theta, x, anc, model.to(gpu.I64)] + ([] if dist is None else [dist])
-                got = gpu.gather_rows_batch(cols, idx[:k_mine])
-                if dist is None:
-                    got.append(tail.distances(got[1], spec.x0vec))
-                for k, v in zip(("theta", "x", "anc", "model", "dist"), got):
-                    kept[k].append(v)
-            if record:
-                rec_x.append(x[:rec_rows].clone() if rec_rows < B // 2 else x[:rec_rows])
-            self._acc_rate = max(int(counts.sum()) / float(B), 1e-6)
-        cols = self._assemble_models(spec, kept, dev, all_accepted)
-        self.nr_evaluations_ = int(led.n_eval)
-        per_model = {m: len(c) for m, c in cols.items()}
-        self.last_stats = dict(rounds=led.rounds, evaluations=int(led.n_eval),
-                               accepted=int(led.n_acc), models=M,
-                               accepted_per_model=per_model,
-                               records_truncated=led.records_truncated)
-        recorded = None
-        if record:
-            recorded = self._gather_recorded(rec_x, led.rec_keeps, dev, 1)
-        elif cols:
-            recorded = torch.cat([c.sum_stats for c in cols.values()])
-        return ModelsSample(cols, recorded, spec.sum_stat_keys, record,
-                            led.n_acc == led.n)
+        return idx, cnt, dist, key, accw
+
+    @staticmethod
+    def _read_count(idx, cnt, kk, B, ws, unfiltered):
+        """(this rank's accept count, the position of the kk-th accepted) of
+        a staged round with at most one host read."""
+        if unfiltered:
+            # idx is arange(B): the k-th kept is candidate k - 1, no read
+            return B, kk - 1
+        if ws == 1:
+            # one read: the count and the index of the n-th accepted
+            # (meaningful only when this round completes the sample)
+            nth = idx[kk - 1:kk] if idx.numel() >= kk else cnt.view(1)
+            return gpu.torch.cat([cnt.view(1), nth]).cpu().tolist()
+        return cnt, None          # gathered on the device, one host read
 
     @staticmethod
     def _simulate_by_model(ms, model, theta, seed, gen, lo, S):
@@ -826,7 +853,7 @@ class BatchedGPUSampler(Sampler):
         return _RoundLedger(n, rank, ws, S, self.max_nr_recorded,
                             self.record_device_budget_bytes)
 
-    def _sample_fused(self, n, fr, spec, max_eval, record, dev, rank, ws):
+    def _sample_fused(self, n, fr, spec, src, max_eval, record, dev, rank, ws):
         """sample_until_n_accepted on fused rounds: per round one
         abc_candidates_round launch (accept bits -> indices of the first
         `need` accepted) and one host read; the kept rows are regenerated
@@ -931,25 +958,25 @@ class BatchedGPUSampler(Sampler):
         if self._acc_rate:
             self._acc_trend = min(1.0, max(0.5, new_rate / self._acc_rate))
         self._acc_rate = new_rate
-        sample = self._finish(spec, led, cols, rec_x if record else None, None,
-                              dev, fr.d, False, fused=True, candidates=int(tot_B),
+        sample = self._finish(led, src, cols, rec_x if record else None, None, dev,
+                              fused=True, candidates=int(tot_B),
                               filtered_rounds=filtered, quantile_reruns=reruns)
         if record and sample._recorded is None:
             # no round recorded a row: an empty matrix here
             sample._recorded = torch.empty((0, S), dtype=gpu.F64, device=dev)
         return sample
 
-    _KEPT = ("theta", "lp", "dist", "x", "anc", "w")   # columns of kept rows
+    _KEPT = ("theta", "lp", "dist", "x", "anc", "w", "model")  # columns of kept rows
 
-    def _finish(self, spec, led, kept, rec_x, rec_extra, dev, d, all_accepted,
-                **stats):
-        """The end of a generation, the same for every loop: the population
-        from the kept rows (kept: lists of per-round pieces under _KEPT), the
-        pending cut resolved and the last recorded pieces trimmed to it,
+    def _finish(self, led, src, kept, rec_x, rec_extra, dev, **stats):
+        """The end of a generation, the same for every loop and source: the
+        population from the kept rows (kept: lists of per-round pieces under
+        _KEPT; src: the candidate source, which assembles them), the pending
+        cut resolved and the last recorded pieces trimmed to it,
         nr_evaluations_ and last_stats (stats: the loop's own keys), the
         recorded rows (rec_x, rec_extra: this rank's pieces; None: the
         generation records nothing) and the sample."""
-        cols, gathered = self._assemble(spec, kept, dev, d, all_accepted, led)
+        cols, gathered, src_stats = src.assemble(kept, led)
         rr = led.finish(gathered)
         if rr is not None:
             rec_x[-1] = rec_x[-1][:rr]
@@ -958,7 +985,7 @@ class BatchedGPUSampler(Sampler):
                                       for a in rec_extra[-1])
         self.nr_evaluations_ = int(led.n_eval)
         self.last_stats = dict(rounds=led.rounds, evaluations=int(led.n_eval),
-                               accepted=int(led.n_acc), **stats,
+                               accepted=int(led.n_acc), **src_stats, **stats,
                                records_truncated=led.records_truncated)
         recorded = records = None
         if rec_x is not None:
@@ -968,10 +995,8 @@ class BatchedGPUSampler(Sampler):
                     None if any(a is None for a in col)
                     else self._gather_recorded(list(col), led.rec_keeps, dev, led.ws)
                     for col in zip(*rec_extra))
-        elif cols is not None:
-            recorded = cols.sum_stats
-        return ColumnarSample(cols, recorded, spec.sum_stat_keys,
-                              rec_x is not None, led.n_acc == led.n, records=records)
+        # (without record_rejected the source gives the population's statistics)
+        return src.sample(cols, recorded, rec_x is not None, led.n_acc == led.n, records)
 
     # population columns of the fused rounds are carved from pooled device
     # arenas: a generation's new population (kept by the History) would

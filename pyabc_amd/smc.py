@@ -71,8 +71,8 @@ class GenerationSpec:
         if isinstance(abc.acceptor, StochasticAcceptor) and not all_accepted:
             self.stochastic = abc.acceptor.device_config(t, self.eps)
         self._closure = None
-        # several models: the per-model description (_init_models), None for
-        # a single model, whose path below is untouched
+        # several models: the per-model description (_init_models); None for
+        # a single model
         self.models = None
         if len(abc.models) > 1:
             self._init_models(abc)
@@ -87,46 +87,46 @@ class GenerationSpec:
             self._eps = self._abc.eps(self.t)
         return self._eps
 
-    def _init_device(self, abc):
+    def _shared_why_not(self, abc):
+        """What keeps a generation off the batched path whatever the number
+        of models: the reasons, in order (a model is named by its number when
+        there are several)."""
+        several = len(abc.models) > 1
         why = []
-        if len(abc.models) != 1:
-            why.append("more than one model")
-        if not isinstance(self.model, VectorizedModel):
-            why.append("model is not a VectorizedModel")
-        elif list(self.model.sum_stat_keys) != self.sum_stat_keys:
-            why.append("model sum_stat_keys differ from x_0 key order")
+        for m, model in enumerate(abc.models):
+            name = f"model {m}" if several else "model"
+            if not isinstance(model, VectorizedModel):
+                why.append(f"{name} is not a VectorizedModel")
+            elif list(model.sum_stat_keys) != self.sum_stat_keys:
+                why.append(f"{name} sum_stat_keys differ from x_0 key order")
         if abc.summary_statistics is not identity:
             why.append("custom summary_statistics function")
         if self.nr_samples_per_parameter != 1:
             why.append("nr_samples_per_parameter != 1")
         if isinstance(abc.acceptor, StochasticAcceptor):
-            if not getattr(abc.distance_function, "batched_capable", False):
+            if several:
+                why.append("StochasticAcceptor with several models")
+            elif not getattr(abc.distance_function, "batched_capable", False):
                 why.append("StochasticAcceptor without a batched noise-model "
                            "kernel")
         elif not isinstance(abc.acceptor, UniformAcceptor) or \
                 abc.acceptor.use_complete_history:
-            why.append("acceptor is not UniformAcceptor(current time) or "
-                       "StochasticAcceptor")
+            why.append("acceptor is not UniformAcceptor(current time)"
+                       + ("" if several else " or StochasticAcceptor"))
         if self.distance is not None and (
                 not hasattr(self.distance, "device_call")
                 or not getattr(self.distance, "batched_capable", True)):
             # (an AggregatedDistance names the child that keeps it on the host)
             why.append(getattr(self.distance, "batched_why_not", "")
                        or "distance has no device kernel")
+        return why
+
+    def _init_device(self, abc):
+        why = self._shared_why_not(abc)
         if self.transition is not None and not hasattr(self.transition,
                                                        "propose_device"):
             why.append("transition has no device kernel")
-        prior = abc.parameter_priors[0]
-        # the prior's device form and host components, computed once per
-        # run() (ABCSMC.run resets the cache; the prior does not change
-        # during a run)
-        cached = abc.__dict__.get("_prior_spec_cache")
-        if cached is not None and cached[0] is prior:
-            spec, host = cached[1], cached[2]
-        else:
-            spec = prior.device_spec() if hasattr(prior, "device_spec") else None
-            host = prior.host_components() if spec is not None else []
-            abc.__dict__["_prior_spec_cache"] = (prior, spec, host)
+        spec, host = _prior_specs(abc)[0]
         if spec is None:
             why.append("prior component without a batched form (not a scipy "
                        "RV, or a discrete / non-frozen scipy distribution "
@@ -136,19 +136,8 @@ class GenerationSpec:
         self.why_not = "; ".join(why)
         self.batched_capable = not why
         if self.batched_capable:
-            # prior and x_0 device constants: uploaded once per run, reused
-            # by every generation (they change only if the prior or x_0 do)
-            x0 = np.array([abc.x_0[k] for k in self.sum_stat_keys], dtype=np.float64)
-            key = (np.asarray(spec[0]).tobytes(), np.asarray(spec[1]).tobytes(),
-                   x0.tobytes())
-            cache = abc.__dict__.setdefault("_device_consts", {})
-            if key not in cache:
-                dev = gpu.require_device()
-                cache.clear()
-                cache[key] = (gpu.as_dev(spec[0], dtype=gpu.torch.int32, device=dev),
-                              gpu.as_dev(spec[1], device=dev),
-                              gpu.as_dev(x0, device=dev))
-            self.prior_kind, self.prior_params, self.x0vec = cache[key]
+            kinds, params, self.x0vec = _device_constants(abc)
+            self.prior_kind, self.prior_params = kinds[0], params[0]
             self.prior_kind_host = tuple(int(k) for k in np.asarray(spec[0]).ravel())
 
     MAX_MODELS = 16          # abc_models_propose
@@ -164,40 +153,11 @@ class GenerationSpec:
         from .sampler import distributed as dd
         t, M = self.t, len(abc.models)
         prior_t = t <= 0 or self.all_accepted
-        why = []
-        if M > self.MAX_MODELS:
-            why.append(f"more than {self.MAX_MODELS} models")
-        for m, model in enumerate(abc.models):
-            if not isinstance(model, VectorizedModel):
-                why.append(f"model {m} is not a VectorizedModel")
-            elif list(model.sum_stat_keys) != self.sum_stat_keys:
-                why.append(f"model {m} sum_stat_keys differ from x_0 key order")
-        if abc.summary_statistics is not identity:
-            why.append("custom summary_statistics function")
-        if self.nr_samples_per_parameter != 1:
-            why.append("nr_samples_per_parameter != 1")
-        if isinstance(abc.acceptor, StochasticAcceptor):
-            why.append("StochasticAcceptor with several models")
-        elif not isinstance(abc.acceptor, UniformAcceptor) or \
-                abc.acceptor.use_complete_history:
-            why.append("acceptor is not UniformAcceptor(current time)")
-        if self.distance is not None and (
-                not hasattr(self.distance, "device_call")
-                or not getattr(self.distance, "batched_capable", True)):
-            why.append(getattr(self.distance, "batched_why_not", "")
-                       or "distance has no device kernel")
+        why = [f"more than {self.MAX_MODELS} models"] if M > self.MAX_MODELS else []
+        why += self._shared_why_not(abc)
         if dd.world()[1] > 1:
             why.append("several ranks with several models")
-        # per-model prior specs, computed once per run() like the single one
-        cached = abc.__dict__.get("_prior_spec_cache")
-        if cached is None or cached[0] is not abc.parameter_priors:
-            specs = [pr.device_spec() if hasattr(pr, "device_spec") else None
-                     for pr in abc.parameter_priors]
-            hosts = [pr.host_components() if sp is not None else []
-                     for pr, sp in zip(abc.parameter_priors, specs)]
-            cached = (abc.parameter_priors, specs, hosts)
-            abc.__dict__["_prior_spec_cache"] = cached
-        specs, hosts = cached[1], cached[2]
+        specs, hosts = zip(*_prior_specs(abc))
         names = [pr.get_parameter_names() for pr in abc.parameter_priors]
         for m in range(M):
             if specs[m] is None:
@@ -242,18 +202,7 @@ class GenerationSpec:
         self.batched_capable = not why
         if not self.batched_capable:
             return
-        x0 = np.array([abc.x_0[k] for k in self.sum_stat_keys], dtype=np.float64)
-        key = ("models", tuple((np.asarray(sp[0]).tobytes(), np.asarray(sp[1]).tobytes())
-                               for sp in specs), x0.tobytes())
-        cache = abc.__dict__.setdefault("_device_consts", {})
-        if key not in cache:
-            dev = gpu.require_device()
-            cache.clear()
-            cache[key] = ([gpu.as_dev(sp[0], dtype=gpu.torch.int32, device=dev)
-                           for sp in specs],
-                          [gpu.as_dev(sp[1], device=dev) for sp in specs],
-                          gpu.as_dev(x0, device=dev))
-        kinds, params, self.x0vec = cache[key]
+        kinds, params, self.x0vec = _device_constants(abc)
         self.models = dict(
             M=M, param_names=names, d=[len(n) for n in names], prior_kind=kinds,
             prior_params=params, transitions=transitions, vmodels=list(abc.models),
@@ -266,6 +215,41 @@ class GenerationSpec:
             else:
                 self._closure = self._abc._create_simulate_function_closure(self.t)
         return self._closure()
+
+
+def _prior_specs(abc):
+    """[(device spec or None, host components)] of the run's parameter
+    priors, one entry per prior, computed once per run() (ABCSMC.run drops
+    the cache; the priors do not change during a run)."""
+    priors = abc.parameter_priors
+    cached = abc.__dict__.get("_prior_spec_cache")
+    if cached is None or len(cached[0]) != len(priors) or \
+            any(a is not b for a, b in zip(cached[0], priors)):
+        specs = [pr.device_spec() if hasattr(pr, "device_spec") else None
+                 for pr in priors]
+        cached = (list(priors), [(sp, pr.host_components() if sp is not None else [])
+                                 for pr, sp in zip(priors, specs)])
+        abc.__dict__["_prior_spec_cache"] = cached
+    return cached[1]
+
+
+def _device_constants(abc):
+    """(prior kinds [per prior], prior params [per prior], x_0 vector) on the
+    device: uploaded once per run and reused by every generation (they change
+    only if a prior or x_0 does, which clears the entry)."""
+    specs = [sp for sp, _ in _prior_specs(abc)]
+    x0 = np.array(list(abc.x_0.values()), dtype=np.float64)
+    key = (tuple((np.asarray(sp[0]).tobytes(), np.asarray(sp[1]).tobytes())
+                 for sp in specs), x0.tobytes())
+    cache = abc.__dict__.setdefault("_device_consts", {})
+    if key not in cache:
+        dev = gpu.require_device()
+        cache.clear()
+        cache[key] = ([gpu.as_dev(sp[0], dtype=gpu.torch.int32, device=dev)
+                       for sp in specs],
+                      [gpu.as_dev(sp[1], device=dev) for sp in specs],
+                      gpu.as_dev(x0, device=dev))
+    return cache[key]
 
 
 def model_proposal_masses(probs, kernel, prior_pmf):
@@ -851,11 +835,9 @@ class ABCSMC:
             theta, dist, key = theta[keep], dist[keep], key[keep]
             anc = None if anc is None else anc[keep]
         if t - 1 == 0:
-            spec = self.parameter_priors[0].device_spec()
-            kinds = gpu.as_dev(spec[0], dtype=gpu.torch.int32, device=theta.device)
-            lp_prev = gpu.prior_logpdf(theta, kinds,
-                                       gpu.as_dev(spec[1], device=theta.device))
-            hl = host_prior_logpdf(theta, self.parameter_priors[0].host_components())
+            kinds, params, _ = _device_constants(self)
+            lp_prev = gpu.prior_logpdf(theta, kinds[0], params[0])
+            hl = host_prior_logpdf(theta, _prior_specs(self)[0][1])
             if hl is not None:
                 lp_prev = lp_prev + hl
         else:

@@ -316,6 +316,48 @@ def test_user_model_accept_tail_equals_staged():
     np.testing.assert_array_equal(pa_["samples"].to_numpy(), pb_["samples"].to_numpy())
 
 
+@pytest.mark.parametrize("accept_tail", [True, False])
+def test_user_model_float32_rows(accept_tail):
+    """A user VectorizedModel that returns float32 rows: the staged loop
+    takes them as their float64 cast in every branch (calibration, accept
+    tail, distance + compaction), so the run equals, bit for bit, the run of
+    a model returning that cast itself, and its statistics are float64."""
+    import pyabc_amd as pa
+    names, keys = ["a", "b", "c"], ["y0", "y1", "y2"]
+
+    def sim(dtype):
+        def run(theta, seed, gen, idx0):
+            g = torch.Generator(device=theta.device)
+            g.manual_seed((seed * 1000003 + gen * 7919 + idx0) % (2 ** 63))
+            x = theta + 0.5 * torch.randn(theta.shape, generator=g, dtype=theta.dtype,
+                                          device=theta.device)
+            return x.to(torch.float32).to(dtype)
+        return run
+
+    def run(dtype):
+        prior = pa.Distribution(**{n: pa.RV("norm", 0, 1) for n in names})
+        sampler = pa.BatchedGPUSampler(seed=13, accept_tail=accept_tail)
+        abc = pa.ABCSMC(pa.VectorizedModel(sim(dtype), keys), prior, pa.PNormDistance(p=2),
+                        population_size=1000, sampler=sampler,
+                        eps=pa.QuantileEpsilon(alpha=0.5))
+        abc.new("sqlite://", {k: 0.7 for k in keys})
+        h = abc.run(max_nr_populations=3)
+        cols = h.get_population_device(h.max_t)
+        assert cols.sum_stats.dtype == torch.float64
+        return ([h.get_distribution(0, t) for t in range(h.max_t + 1)],
+                h.get_all_populations(), cols.sum_stats.cpu().numpy())
+    a, pa_, xa = run(torch.float32)
+    b, pb_, xb = run(torch.float64)
+    assert len(a) == len(b) == 3
+    for (df1, w1), (df2, w2) in zip(a, b):
+        np.testing.assert_array_equal(df1[names].to_numpy(), df2[names].to_numpy())
+        np.testing.assert_array_equal(w1, w2)
+    np.testing.assert_array_equal(xa, xb)
+    np.testing.assert_array_equal(xa, xa.astype(np.float32).astype(np.float64))
+    np.testing.assert_array_equal(pa_["epsilon"].to_numpy(), pb_["epsilon"].to_numpy())
+    np.testing.assert_array_equal(pa_["samples"].to_numpy(), pb_["samples"].to_numpy())
+
+
 def test_local_transition_d80_generations():
     """ABCSMC with LocalTransition at d = 80 (> 64: staged rounds with the
     wide propose kernel, the BIG fit and density): every generation's

@@ -169,3 +169,161 @@ def test_why_not_names_each_excluded_case(monkeypatch):
     one.x_0 = {"y0": 0.0}
     spec = pa.GenerationSpec(one, 0)
     assert spec.models is None and spec.why_not == "model is not a VectorizedModel"
+
+
+# ---- the multi-model candidate source on the staged loop (CPU doubles) --------
+
+_SEED, _S, _BATCH, _N_REPLAY = 4242, 3, 300, 1800
+_MODELS = [dict(kinds=["uniform"], params=[[0.0, 1.0, 0, 0]]),
+           dict(kinds=["norm", "norm"], params=[[0.0, 1.0, 0, 0]] * 2)]
+_SRC = np.array([[0, 0, 0], [0, 1, 0]])
+_A = np.array([[1.0, -1.0, 0.5], [1.0, 1.0, -1.0]])
+_SIGMA = np.full((2, _S), 0.5)
+_EPS = 1.0
+
+
+def _pnorm_np(x, x0, wf, p):
+    return (np.abs(wf * (x - x0)) ** p).sum(1) ** (1.0 / p)
+
+
+@pytest.fixture(scope="module")
+def models_replay():
+    """The first _N_REPLAY candidates of generation 0 (candidates are keyed by
+    their global index, so rounds of any size see these rows)."""
+    model, theta, anc, att, _ = mref.propose(_MODELS, [0.5, 1.0], _SEED, 0, 0, _N_REPLAY,
+                                             10000)
+    x = mref.simulate(theta, model, _SRC, _A, _SIGMA, _SEED, 0, 0)
+    d = _pnorm_np(x, np.zeros(_S), np.ones(_S), 2.0)
+    return dict(model=model, theta=theta, x=x, d=d, acc=np.nonzero(d <= _EPS)[0])
+
+
+class _TableModel:
+    def __init__(self, m):
+        self.m = m
+
+    def fused_simulator(self, dev):
+        import torch
+        return (torch.tensor(_SRC[self.m], dtype=torch.int32),
+                torch.tensor(_A[self.m]), torch.tensor(_SIGMA[self.m]))
+
+
+class _ModelsSpec:
+    """What the staged loop reads of a GenerationSpec over two models at
+    t = 0 (no transitions: the weights are ones)."""
+    batched_capable = True
+
+    def __init__(self):
+        import torch
+        import pyabc_amd as pa
+        self.t = 0
+        self.sum_stat_keys = [f"y{k}" for k in range(_S)]
+        self.distance = pa.PNormDistance(p=2)
+        self.x0vec = torch.zeros(_S, dtype=torch.float64)
+        self.eps = _EPS
+        self.weight_scale = 1.0
+        self.models = dict(
+            M=2, d=[1, 2], param_names=[["a"], ["a", "b"]],
+            prior_kind=[torch.zeros(d, dtype=torch.int32) for d in (1, 2)],
+            prior_params=[torch.zeros(4 * d, dtype=torch.float64) for d in (1, 2)],
+            transitions=[None, None], vmodels=[_TableModel(0), _TableModel(1)],
+            model_cdf=np.array([0.5, 1.0]), masses=np.array([0.5, 0.5]),
+            log_scale=np.zeros(2))
+
+
+def _install_models_doubles(monkeypatch):
+    """The device calls of a multi-model staged round as the numpy replay
+    (models_ref) and index arithmetic, on host tensors."""
+    import torch
+    from pyabc_amd.sampler import batched
+    g = batched.gpu
+    t = torch.from_numpy
+
+    class ModelSet:
+        def __init__(self, descs, model_cdf, seed, generation, max_attempts):
+            self.args = (model_cdf, seed, generation)
+            self.max_attempts = max_attempts
+
+        def propose(self, idx0, B):
+            model, theta, anc, att, _ = mref.propose(_MODELS, *self.args, idx0, B,
+                                                     self.max_attempts)
+            return t(model).to(torch.int32), t(theta), t(anc), t(att).to(torch.int32)
+
+    def simulate(theta, model, src, a, sigma, seed, generation, idx0):
+        return t(mref.simulate(theta.numpy(), model.numpy(), src.numpy(), a.numpy(),
+                               sigma.numpy(), seed, generation, idx0))
+
+    def partition(model, M):
+        perm, counts = mref.partition(model.numpy(), M)
+        return t(perm), t(counts)
+
+    def pnorm(x, x0, wf, pv, out=None):
+        return t(_pnorm_np(x.numpy(), x0.numpy(), wf.numpy(), pv))
+
+    def pnorm_accept(x, x0, wf, pv, eps, cap, att=None, max_attempts=0):
+        d = _pnorm_np(x.numpy(), x0.numpy(), wf.numpy(), pv)
+        acc = np.nonzero((d <= eps) & (att.numpy() <= max_attempts))[0]
+        idx = torch.zeros(max(int(cap), 1), dtype=torch.int64)
+        k = min(int(cap), len(acc))
+        idx[:k] = t(acc[:k])
+        return idx, torch.tensor([len(acc)])
+
+    def accept_compact(d, eps):
+        idx = torch.nonzero(d <= eps).flatten().to(torch.int64)
+        return idx, torch.tensor([idx.numel()])
+
+    def mask_gave_up(dist, att, max_attempts, value=float("nan")):
+        dist[att > max_attempts] = value
+        return dist
+
+    for name, fn in dict(
+            ModelSet=ModelSet, models_simulate_linear_gaussian=simulate,
+            models_partition=partition, pnorm=pnorm, pnorm_accept=pnorm_accept,
+            accept_compact=accept_compact, mask_gave_up=mask_gave_up,
+            require_device=lambda: torch.device("cpu"),
+            gather_rows=lambda x, idx, n=None: x.index_select(0, idx),
+            gather_rows_batch=lambda arrays, idx, n=None: [a.index_select(0, idx)
+                                                           for a in arrays]).items():
+        monkeypatch.setattr(g, name, fn)
+
+
+@pytest.mark.parametrize("record", [False, True])
+@pytest.mark.parametrize("accept_tail", [True, False])
+def test_models_source_on_the_staged_loop(monkeypatch, models_replay, accept_tail, record):
+    """BatchedGPUSampler's staged loop with its multi-model candidate source
+    (M = 2, d = (1, 2), S = 3, t = 0) on one rank, the device calls replaced
+    by the replay: n = 200 at 300 candidates per round takes 3 rounds and
+    cuts the last one in the middle.  The kept rows are the replay's first
+    200 accepted, split by model in candidate order; the evaluations end at
+    the 200th accepted; the recorded matrix is every row up to it; the accept
+    tail and the distance + compaction branch give the same sample."""
+    from pyabc_amd.sampler import BatchedGPUSampler
+    n, rp = 200, models_replay
+    acc = rp["acc"]
+    assert 0.15 <= len(acc) / _N_REPLAY <= 0.40
+    _install_models_doubles(monkeypatch)
+    s = BatchedGPUSampler(batch_size=_BATCH, seed=_SEED, accept_tail=accept_tail)
+    s.sample_factory.record_rejected = record
+    sample = s.sample_until_n_accepted(n, _ModelsSpec())
+    assert sample.ok and sample.n_accepted == n
+    assert s.last_stats["rounds"] >= 2
+    assert s.nr_evaluations_ == acc[n - 1] + 1
+    assert s.nr_evaluations_ % _BATCH not in (0, 1, _BATCH - 1)    # cut mid-round
+    first = acc[:n]
+    per_model = {}
+    for m, d in enumerate((1, 2)):
+        rows = first[rp["model"][first] == m]
+        per_model[m] = len(rows)
+        c = sample._mcols[m]
+        np.testing.assert_array_equal(c.theta.numpy(), rp["theta"][rows, :d])
+        np.testing.assert_array_equal(c.sum_stats.numpy(), rp["x"][rows])
+        np.testing.assert_array_equal(c.distances.numpy(), rp["d"][rows])
+        np.testing.assert_array_equal(c.weights.numpy(), np.ones(len(rows)))
+        assert c.param_names == [["a"], ["a", "b"]][m] and c.m == m
+    assert min(per_model.values()) > 0
+    assert s.last_stats["accepted_per_model"] == per_model
+    assert s.last_stats["models"] == 2 and s.last_stats["accepted"] == n
+    assert s.last_stats["evaluations"] == s.nr_evaluations_
+    assert not s.last_stats["records_truncated"]
+    want = (rp["x"][:s.nr_evaluations_] if record else
+            np.concatenate([rp["x"][first[rp["model"][first] == m]] for m in (0, 1)]))
+    np.testing.assert_array_equal(sample._recorded.numpy(), want)
