@@ -817,6 +817,81 @@ int abc_comm_allreduce(void* comm, const void* send, void* recv, size_t count,
                        int dtype, int op, void* stream);
 int abc_comm_broadcast(void* comm, void* buf, size_t bytes, int root, void* stream);
 
+/* ---- integer parameters: grid priors and the discrete random walk ---------
+ * (abc_walk.hip)  Parameters stay float64 columns whose values are integers.
+ *
+ * Grid prior: per coordinate k a table over the consecutive integers k_lo ..
+ * k_lo + len - 1.  A host struct of device pointers:
+ *   coord  [d x 4] int64: k_lo, len, offset (of the coordinate's tables in
+ *          logpmf / cdf), last (largest table index of positive mass);
+ *   logpmf, cdf: the concatenated tables; cdf is the host's running sum of
+ *          the pmf per coordinate (numpy.cumsum), so a replay searches the
+ *          same bits.  d <= 64. */
+typedef struct abc_grid_prior {
+  int d;
+  const int64_t* coord;
+  const double* logpmf;
+  const double* cdf;
+} abc_grid_prior;
+/* Distribution.pdf (pyabc/random_variables.py:425-452) in log space:
+ * lp[b] = sum over k, in ascending k, of logpmf_k[theta[b, k] - k_lo_k];
+ * a coordinate outside its window contributes -inf, one that is not an
+ * integer (or is NaN) NaN. */
+int abc_grid_prior_logpmf(const double* theta, int64_t B,
+                          const abc_grid_prior* prior, double* lp, void* stream);
+/* prior.rvs() (pyabc/smc.py:624-626) for candidates idx0 .. idx0 + B - 1:
+ * theta[b, k] = k_lo_k + min(first i with cdf_k[i] >= u cdf_k[len - 1], last),
+ * u the (0, 1) uniform abc_prior_uniforms returns for (candidate, k, first
+ * attempt).  An entry of mass 0 is never the first, so every draw has
+ * positive mass: no re-draw. */
+int abc_grid_prior_draw(const abc_grid_prior* prior, uint64_t seed,
+                        uint32_t generation, int64_t idx0, int64_t B,
+                        double* theta, void* stream);
+
+/* DiscreteRandomWalkTransition (pyabc/transition/randomwalk.py:42-81).
+ * Limits of the walk entries: d <= ABC_WALK_MAX_D, n_steps <=
+ * ABC_WALK_MAX_STEPS (ABC_ERR_UNSUPPORTED beyond them).
+ * abc_walk_pack: Xi[e] = (int32) X[e] for the N d entries of the population;
+ *   *bad (device int64, written by the call) = the number of entries that
+ *   are not integers, are NaN or exceed 2^30 in magnitude (the fit raises
+ *   the reference's ValueError, randomwalk.py:55-59; with the cap the
+ *   difference of two coordinates fits an int32). */
+#define ABC_WALK_MAX_D 32
+#define ABC_WALK_MAX_STEPS 512
+int abc_walk_pack(const double* X, int64_t N, int d, int32_t* Xi, int64_t* bad,
+                  void* stream);
+/* rvs_single (randomwalk.py:42-53) for candidates idx0 .. : attempt a uses
+ * the slots from a * 65536; ancestor j as in abc_propose (words 0, 1 of the
+ * attempt's first slot over cdf / guide); theta_k = Xi[j, k] + s_k, s_k drawn
+ * in one step from the law of the net displacement of n_steps steps:
+ * s_k = min(first i with law_cum[i] > u law_cum[2 n], law_last) - n, law_cum
+ * [2 n + 1] the host's running sum of the law (index s + n), law_last the
+ * largest index of positive law, u the 53-bit [0, 1) uniform of words
+ * 2 (k & 1), 2 (k & 1) + 1 of slot 1 + (k >> 1) of the attempt.  The attempt
+ * is re-drawn while the grid prior's log mass is -inf (smc.py:654-656), at
+ * most max_attempts times (attempts > max_attempts: gave up, prior_logpmf
+ * -inf).  prior NULL: plain rvs, one attempt.  prior_logpmf nullable. */
+int abc_walk_propose(const int32_t* Xi, const double* cdf, const int32_t* guide,
+                     int64_t N, int d, const double* law_cum, int n_steps,
+                     int law_last, const abc_grid_prior* prior, uint64_t seed,
+                     uint32_t generation, int64_t idx0, int64_t B,
+                     int max_attempts, double* theta, double* prior_logpmf,
+                     int64_t* ancestor, int32_t* attempts, void* stream);
+/* pdf (randomwalk.py:55-81): out[i] = log sum_j w_j prod_k law[x_ik - Xi_jk +
+ * n], -inf where the sum is 0; a candidate coordinate that is not an integer
+ * gives NaN, one beyond 2^30 in magnitude is taken as further than n_steps
+ * from every particle (mass 0).  The product runs over k in ascending order and is then
+ * multiplied by w_j; the particles are summed in ascending order within a
+ * chunk of abc_walk_logpmf_chunk(M, N, d) particles (a function of the
+ * shape alone) and the chunks in ascending order: the same bits on every
+ * call. */
+int64_t abc_walk_logpmf_chunk(int64_t M, int64_t N, int d);
+size_t abc_walk_logpmf_bytes(int64_t M, int64_t N, int d);
+int abc_walk_logpmf(const double* x, int64_t M, const int32_t* Xi,
+                    const double* w, int64_t N, int d, const double* law,
+                    int n_steps, double* out, void* ws, size_t ws_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,14 @@ SIGNATURES = {
     "abc_comm_allgather": (I32, [P, P, P, SZ, P]),
     "abc_comm_allreduce": (I32, [P, P, P, SZ, I32, I32, P]),
     "abc_comm_broadcast": (I32, [P, P, SZ, I32, P]),
+    "abc_grid_prior_logpmf": (I32, [P, I64, P, P, P]),
+    "abc_grid_prior_draw": (I32, [P, U64, U32, I64, I64, P, P]),
+    "abc_walk_pack": (I32, [P, I64, I32, P, P, P]),
+    "abc_walk_propose": (I32, [P, P, P, I64, I32, P, I32, I32, P, U64, U32, I64, I64,
+                               I32, P, P, P, P, P]),
+    "abc_walk_logpmf_chunk": (I64, [I64, I64, I32]),
+    "abc_walk_logpmf_bytes": (SZ, [I64, I64, I32]),
+    "abc_walk_logpmf": (I32, [P, I64, P, P, I64, I32, P, I32, P, P, SZ, P]),
 }
 
 
@@ -140,7 +148,14 @@ class ModelDesc(C.Structure):
                 ("support_box", P)]
 
 
+class GridPrior(C.Structure):
+    """abc_grid_prior (include/abcgpu.h), field for field."""
+    _fields_ = [("d", C.c_int), ("coord", P), ("logpmf", P), ("cdf", P)]
+
+
 ABC_MODELS_MAX = 16
+ABC_WALK_MAX_D = 32
+ABC_WALK_MAX_STEPS = 512
 
 # C error codes (include/abcgpu.h)
 ABC_OK = 0

@@ -1032,3 +1032,98 @@ def temper_sums(dens, lr, pdf_norm, scale_log, mode, beta=0.0, shift=0.0,
              p(out), p(ws), ws.numel(), stream_ptr())
     a, b = out.cpu().numpy()
     return float(a), float(b)
+
+
+# ---- integer parameters: grid priors and the discrete random walk ----------
+
+class GridPrior:
+    """Device tables of a grid prior (abc_grid_prior) from
+    ``Distribution.grid_spec()``: per coordinate (k_lo, pmf, logpmf) in
+    sorted-name order.  The scan of each pmf is numpy's cumsum, made here on
+    the host, so a replay of the draws searches the same bits."""
+
+    def __init__(self, spec, device=None):
+        import ctypes as C
+        device = device or require_device()
+        coord, lps, cdfs, off = [], [], [], 0
+        for k_lo, pmf, logpmf in spec:
+            pmf = np.asarray(pmf, dtype=np.float64)
+            pos = np.nonzero(pmf > 0)[0]
+            if pmf.ndim != 1 or len(pos) == 0 or len(logpmf) != len(pmf):
+                raise ValueError("GridPrior: a coordinate needs a 1-d table of "
+                                 "positive total mass")
+            coord.append((int(k_lo), len(pmf), off, int(pos[-1])))
+            lps.append(np.asarray(logpmf, dtype=np.float64))
+            cdfs.append(np.cumsum(pmf))
+            off += len(pmf)
+        self.d = len(coord)
+        self.coord_host = np.asarray(coord, dtype=np.int64)
+        self.cdf_host = cdfs
+        self.coord = as_dev(self.coord_host, dtype=I64, device=device)
+        self.logpmf = as_dev(np.concatenate(lps), device=device)
+        self.cdf = as_dev(np.concatenate(cdfs), device=device)
+        self.device = device
+        self.desc = nat.GridPrior(self.d, p(self.coord), p(self.logpmf), p(self.cdf))
+        self.ref = C.addressof(self.desc)
+
+    def logpmf_rows(self, theta, out=None):
+        """Log prior mass of the rows of theta [B, d] (abc_grid_prior_logpmf)."""
+        B, d = theta.shape
+        if d != self.d:
+            raise ValueError("GridPrior: theta has the wrong number of columns")
+        out = torch.empty(B, dtype=F64, device=theta.device) if out is None else out
+        nat.call("abc_grid_prior_logpmf", p(theta) if B else None, B, self.ref,
+                 p(out) if B else None, stream_ptr())
+        return out
+
+    def draw(self, seed, generation, idx0, B):
+        """Prior draws of candidates idx0 .. idx0 + B - 1 (abc_grid_prior_draw)."""
+        theta = torch.empty((int(B), self.d), dtype=F64, device=self.device)
+        nat.call("abc_grid_prior_draw", self.ref, int(seed) & (2 ** 64 - 1),
+                 int(generation) & 0xFFFFFFFF, int(idx0), int(B),
+                 p(theta) if B else None, stream_ptr())
+        return theta
+
+
+def walk_pack(X):
+    """(Xi int32 [N, d], device int64 count of entries that are no integers
+    within +-2^30) of a population X [N, d] (abc_walk_pack)."""
+    N, d = X.shape
+    Xi = torch.empty((N, d), dtype=torch.int32, device=X.device)
+    bad = torch.empty(1, dtype=I64, device=X.device)
+    nat.call("abc_walk_pack", p(X), N, d, p(Xi), p(bad), stream_ptr())
+    return Xi, bad
+
+
+def walk_propose(Xi, cdf, guide, law_cum, n_steps, law_last, seed, generation, idx0,
+                 B, max_attempts=1, grid_prior=None):
+    """(theta, prior log mass, ancestor, attempts) of B random-walk proposals
+    (abc_walk_propose); grid_prior: a GridPrior or None (plain rvs)."""
+    N, d = Xi.shape
+    dev, B = Xi.device, int(B)
+    theta = torch.empty((B, d), dtype=F64, device=dev)
+    lp = torch.empty(B, dtype=F64, device=dev)
+    anc = torch.empty(B, dtype=I64, device=dev)
+    att = torch.empty(B, dtype=torch.int32, device=dev)
+    nat.call("abc_walk_propose", p(Xi), p(cdf), p(guide), N, d, p(law_cum), int(n_steps),
+             int(law_last), None if grid_prior is None else grid_prior.ref,
+             int(seed) & (2 ** 64 - 1), int(generation) & 0xFFFFFFFF, int(idx0), B,
+             int(max_attempts), p(theta), p(lp), p(anc), p(att), stream_ptr())
+    return theta, lp, anc, att
+
+
+def walk_logpmf_chunk(M, N, d):
+    """Particles per chunk of abc_walk_logpmf's sum for this shape."""
+    return int(nat.load().abc_walk_logpmf_chunk(int(M), int(N), int(d)))
+
+
+def walk_logpmf(x, Xi, w, law, n_steps, out=None):
+    """log sum_j w_j prod_k law[x_ik - Xi_jk + n] per row of x [M, d]
+    (abc_walk_logpmf)."""
+    M, d = x.shape
+    N = Xi.shape[0]
+    out = torch.empty(M, dtype=F64, device=x.device) if out is None else out
+    ws = workspace(nat.query("abc_walk_logpmf_bytes", M, N, d), "walk")
+    nat.call("abc_walk_logpmf", p(x), M, p(Xi), p(w), N, d, p(law), int(n_steps), p(out),
+             p(ws), ws.numel(), stream_ptr())
+    return out

@@ -17,10 +17,17 @@ device prior kinds of include/abcgpu.h:
   and the draws stay keyed by the global candidate index.
 
 The HOST kind assumes the density is positive inside the support interval
-(true of scipy's continuous families).  Discrete distributions outside the
-device families and non-frozen scipy objects have no batched form
-(``device_spec`` is None): such priors run the per-candidate loop, which
-re-draws until the prior density is positive as the reference does.
+(true of scipy's continuous families).  Discrete distributions and non-frozen
+scipy objects have no such description (``device_spec`` is None).
+
+Integer parameters take a second batched form, the grid prior: a frozen
+``rv_discrete`` with integer ``loc`` becomes a table over the consecutive
+integers of positive mass (``grid_spec``; at most 2^20 entries per
+coordinate), evaluated and sampled by abc_grid_prior_logpmf / _draw and
+paired with DiscreteRandomWalkTransition.  A prior is either all grid or all
+continuous; anything else (mixed priors, decorated components, a window
+above the cap) runs the per-candidate loop, which re-draws until the prior
+density is positive as the reference does.
 """
 import logging
 from abc import ABC, abstractmethod
@@ -174,6 +181,72 @@ class RV(RVBase):
         vals = [float(v) for v in (*shapes, loc, scale)]
         return vals + [0.0] * (4 - len(vals))
 
+    GRID_MAX = 1 << 20       # entries of one coordinate's table
+
+    def grid_spec(self):
+        """``(spec, why)``: the component as a table over consecutive
+        integers for the batched sampler's grid prior, ``spec = (k_lo,
+        pmf[len], logpmf[len])``, or ``(None, reason)`` when it has no such
+        form.  The window is every integer from the first to the last k with
+        scipy's ``pmf(k) > 0`` in float64, found by doubling outwards from
+        ``ppf(0.5)`` and bisecting (a ``rv_discrete(values=...)``: between
+        its own points); entries of mass 0 inside it stay in the table with
+        log mass -inf."""
+        import scipy.stats
+        frozen = self.distribution
+        if not isinstance(frozen, scipy.stats._distn_infrastructure.rv_frozen):
+            return None, "not a frozen scipy distribution"
+        if not isinstance(frozen.dist, scipy.stats.rv_discrete):
+            return None, "continuous distribution"
+        try:
+            _, loc, _ = frozen.dist._parse_args(*frozen.args, **frozen.kwds)
+        except Exception as err:      # a parametrisation scipy itself refuses
+            return None, f"parameters not understood ({err})"
+        if not (np.isfinite(loc) and float(loc) == np.floor(loc)):
+            return None, f"non-integer loc {loc}"
+        pmf1 = lambda k: float(frozen.pmf(k))
+        xk = getattr(frozen.dist, "xk", None)
+        if xk is not None:
+            # rv_discrete(values=...): its points may have gaps of mass 0
+            pts = np.asarray(xk, dtype=np.float64) + float(loc)
+            if not np.all(pts == np.floor(pts)):
+                return None, "non-integer support points"
+            pos = [int(k) for k in pts if pmf1(k) > 0]
+            if not pos:
+                return None, "no point of positive mass"
+            k_lo, k_hi = min(pos), max(pos)
+        else:
+            mid = frozen.ppf(0.5)
+            if not np.isfinite(mid) or not pmf1(int(mid)) > 0:
+                return None, "no mass at the median"
+            mid = int(mid)
+            ends = []
+            for sign in (-1, 1):
+                # doubling: good has mass, bad has none; then bisect
+                good, step = mid, 1
+                while pmf1(mid + sign * step) > 0:
+                    good, step = mid + sign * step, 2 * step
+                    if step > 2 * self.GRID_MAX:
+                        return None, "window above 2^20 entries"
+                bad = mid + sign * step
+                while abs(bad - good) > 1:
+                    m = (good + bad) // 2
+                    if pmf1(m) > 0:
+                        good = m
+                    else:
+                        bad = m
+                ends.append(good)
+            k_lo, k_hi = ends
+        if k_hi - k_lo + 1 > self.GRID_MAX:
+            return None, "window above 2^20 entries"
+        if max(abs(k_lo), abs(k_hi)) > 2 ** 30:
+            return None, "window beyond +-2^30"
+        ks = np.arange(k_lo, k_hi + 1)
+        pmf = np.asarray(frozen.pmf(ks), dtype=np.float64)
+        with np.errstate(divide="ignore"):
+            logpmf = np.where(pmf > 0, frozen.logpmf(ks), -np.inf)
+        return (int(k_lo), pmf, logpmf), ""
+
     def host_logpdf(self, x):
         """Vectorised log density (log pmf for discrete families)."""
         x = np.asarray(x, dtype=np.float64)
@@ -210,6 +283,9 @@ class RVDecorator(RVBase):
 
     def copy(self):
         return type(self)(self.component.copy())
+
+    def grid_spec(self):
+        return None, "decorated component (RVDecorator)"
 
     def decorator_repr(self) -> str:
         return "Decorator"
@@ -318,6 +394,24 @@ class Distribution(ParameterStructure):
             kinds.append(kind)
             params.extend(par)
         return np.asarray(kinds, dtype=np.int32), np.asarray(params, np.float64)
+
+    def grid_spec(self):
+        """``(specs, why)``: every component's ``RV.grid_spec()`` table in
+        sorted-name order, or ``(None, "<name>: <reason>")`` naming the first
+        component without one.  A prior has a grid form only if every
+        component has (no mixed continuous / discrete priors)."""
+        specs = []
+        for name in self.get_parameter_names():
+            rv = self[name]
+            if not hasattr(rv, "grid_spec"):
+                return None, f"{name}: not a scipy RV"
+            spec, why = rv.grid_spec()
+            if spec is None:
+                return None, f"{name}: {why}"
+            specs.append(spec)
+        if not specs:
+            return None, "no parameters"
+        return specs, ""
 
     def host_components(self):
         """[(column, RV)] of the components on the host-scipy leg

@@ -340,6 +340,39 @@ class _OneModelSource:
                               records=records)
 
 
+class _GridSource(_OneModelSource):
+    """Candidate source of a one-model generation over integer parameters: a
+    grid prior (abc_grid_prior_draw at t = 0, abc_grid_prior_logpmf on the
+    kept rows) and DiscreteRandomWalkTransition.propose_device afterwards.
+    It builds no CandidateRound and never takes the fused round; the staged
+    loop, the ledger, the accept tails and the ranks' gather are
+    _OneModelSource's."""
+
+    def __init__(self, sampler, spec, seed, gen, dev, all_accepted):
+        super().__init__(sampler, spec, seed, gen, dev, all_accepted)
+        self.prior = spec.grid_prior
+
+    def propose(self, lo, B):
+        if self.spec.transition is None:
+            theta = self.prior.draw(self.seed, self.gen, lo, B)
+            return dict(theta=theta, lp=None, anc=None), None
+        theta, _, anc, att = self.spec.transition.propose_device(
+            B, self.prior, seed=self.seed, generation=self.gen, idx0=lo,
+            max_attempts=self.sampler.max_attempts)
+        # the prior log mass only for the rows kept (complete)
+        return dict(theta=theta, lp=None, anc=anc), att
+
+    def complete(self, got, att, unfiltered):
+        if "lp" in got:
+            return
+        got["lp"] = self.prior.logpmf_rows(got["theta"])
+        if unfiltered and att is not None:
+            # rows kept unfiltered include proposals that exhausted
+            # max_attempts: the proposal kernel's log mass for them is -inf
+            gpu.mask_gave_up(got["lp"], att[:got["lp"].numel()],
+                             self.sampler.max_attempts, -np.inf)
+
+
 class _ModelsSource:
     """Candidate source of a generation over M > 1 models (one rank).  A
     round proposes (model, theta) per candidate (abc_models_propose: the
@@ -527,6 +560,8 @@ class BatchedGPUSampler(Sampler):
         record = self.sample_factory.record_rejected
         if getattr(spec, "models", None) is not None:
             src = _ModelsSource(self, spec, seed, gen, dev, all_accepted)
+        elif getattr(spec, "grid", None) is not None:
+            src = _GridSource(self, spec, seed, gen, dev, all_accepted)
         else:
             src = _OneModelSource(self, spec, seed, gen, dev, all_accepted)
             fr = None if all_accepted else self._fused_round(spec, seed, gen, dev)
@@ -770,6 +805,8 @@ class BatchedGPUSampler(Sampler):
         if not self.fused or getattr(spec, "stochastic", None) is not None \
                 or spec.distance is None or len(spec.param_names) > self.FUSED_MAX_DIM:
             return None
+        if getattr(spec, "grid", None) is not None:
+            return None     # integer parameters: staged path (_GridSource)
         if spec.transition is None and getattr(spec, "host_prior", None):
             return None     # t = 0 draws of host-leg coordinates: staged path
         sim = (spec.model.fused_simulator(dev)
@@ -1059,6 +1096,8 @@ class BatchedGPUSampler(Sampler):
         # reused by a later run's spec while the entry lives)
         if len(spec.param_names) > self.FUSED_MAX_DIM:
             return None     # d > 64: the transition's own (wide) proposal kernel
+        if getattr(spec, "grid", None) is not None:
+            return None     # a grid prior has no device kinds (_GridSource)
         key = (seed, gen)
         if self._prop[0] is spec and self._prop[1] == key:
             return self._prop[2]

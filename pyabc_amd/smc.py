@@ -30,7 +30,8 @@ from .populationstrategy import ConstantPopulationSize, PopulationStrategy
 from .random_variables import RV, Distribution, host_prior_logpdf
 from .sampler import BatchedGPUSampler, Sampler, SingleCoreSampler
 from .storage import History
-from .transition import MultivariateNormalTransition, Transition
+from .transition import (DiscreteRandomWalkTransition,
+                         MultivariateNormalTransition, Transition)
 from .weighted_statistics import effective_sample_size
 
 logger = logging.getLogger("ABC")
@@ -74,6 +75,8 @@ class GenerationSpec:
         # several models: the per-model description (_init_models); None for
         # a single model
         self.models = None
+        # a grid prior's host tables (_init_device; None: continuous prior)
+        self.grid = None
         if len(abc.models) > 1:
             self._init_models(abc)
         else:
@@ -123,22 +126,49 @@ class GenerationSpec:
 
     def _init_device(self, abc):
         why = self._shared_why_not(abc)
+        walk = isinstance(self.transition, DiscreteRandomWalkTransition)
         if self.transition is not None and not hasattr(self.transition,
                                                        "propose_device"):
             why.append("transition has no device kernel")
         spec, host = _prior_specs(abc)[0]
-        if spec is None:
+        # integer parameters: the prior as tables over consecutive integers
+        # (Distribution.grid_spec), proposals by DiscreteRandomWalkTransition
+        grid, grid_why = (None, "") if spec is not None else _grid_specs(abc)[0]
+        if spec is None and grid is None:
             why.append("prior component without a batched form (not a scipy "
                        "RV, or a discrete / non-frozen scipy distribution "
-                       "outside the device families)")
+                       "outside the device families) and without a grid form"
+                       + (f" ({grid_why})" if grid_why else ""))
+        if grid is not None and self.transition is not None:
+            if not walk:
+                why.append("grid prior with a transition that is not a "
+                           "DiscreteRandomWalkTransition (a continuous "
+                           "proposal never has positive prior mass)")
+            else:
+                lim = self.transition.device_why_not(len(self.param_names))
+                if lim:
+                    why.append(lim)
+                elif getattr(self.transition, "_dev_Xi", None) is None:
+                    why.append("DiscreteRandomWalkTransition not fitted on "
+                               "the device")
+        if spec is not None and walk:
+            why.append("DiscreteRandomWalkTransition with a continuous prior")
         # components without a device sampler: host-scipy density / draws
         self.host_prior = host
+        self.grid = grid
         self.why_not = "; ".join(why)
         self.batched_capable = not why
         if self.batched_capable:
             kinds, params, self.x0vec = _device_constants(abc)
             self.prior_kind, self.prior_params = kinds[0], params[0]
-            self.prior_kind_host = tuple(int(k) for k in np.asarray(spec[0]).ravel())
+            if grid is None:
+                self.prior_kind_host = tuple(int(k) for k in np.asarray(spec[0]).ravel())
+
+    @property
+    def grid_prior(self):
+        """The device tables (gpu.GridPrior) of a grid generation's prior,
+        uploaded once per run."""
+        return None if self.grid is None else _grid_prior_device(self._abc)
 
     MAX_MODELS = 16          # abc_models_propose
     MAX_MODEL_DIM = 64
@@ -160,7 +190,10 @@ class GenerationSpec:
         specs, hosts = zip(*_prior_specs(abc))
         names = [pr.get_parameter_names() for pr in abc.parameter_priors]
         for m in range(M):
-            if specs[m] is None:
+            if specs[m] is None and _grid_specs(abc)[m][0] is not None:
+                why.append(f"prior of model {m} is a grid prior (several "
+                           "models)")
+            elif specs[m] is None:
                 why.append(f"prior of model {m} has a component without a "
                            "batched form")
             elif hosts[m]:
@@ -233,21 +266,51 @@ def _prior_specs(abc):
     return cached[1]
 
 
+def _grid_specs(abc):
+    """[(grid tables or None, reason)] of the run's parameter priors
+    (Distribution.grid_spec), computed once per run like _prior_specs."""
+    priors = abc.parameter_priors
+    cached = abc.__dict__.get("_grid_spec_cache")
+    if cached is None or len(cached[0]) != len(priors) or \
+            any(a is not b for a, b in zip(cached[0], priors)):
+        cached = (list(priors),
+                  [pr.grid_spec() if hasattr(pr, "grid_spec")
+                   else (None, "not a Distribution") for pr in priors])
+        abc.__dict__["_grid_spec_cache"] = cached
+        abc.__dict__.pop("_grid_prior_dev", None)
+    return cached[1]
+
+
+def _grid_prior_device(abc):
+    """gpu.GridPrior of the (single) prior's grid tables, uploaded once per
+    run."""
+    grid = _grid_specs(abc)[0][0]
+    cached = abc.__dict__.get("_grid_prior_dev")
+    if cached is None or cached[0] is not grid:
+        cached = (grid, gpu.GridPrior(grid, gpu.require_device()))
+        abc.__dict__["_grid_prior_dev"] = cached
+    return cached[1]
+
+
 def _device_constants(abc):
     """(prior kinds [per prior], prior params [per prior], x_0 vector) on the
     device: uploaded once per run and reused by every generation (they change
-    only if a prior or x_0 does, which clears the entry)."""
+    only if a prior or x_0 does, which clears the entry).  A prior without
+    device kinds (a grid prior) has None for both."""
     specs = [sp for sp, _ in _prior_specs(abc)]
     x0 = np.array(list(abc.x_0.values()), dtype=np.float64)
-    key = (tuple((np.asarray(sp[0]).tobytes(), np.asarray(sp[1]).tobytes())
+    key = (tuple(None if sp is None else
+                 (np.asarray(sp[0]).tobytes(), np.asarray(sp[1]).tobytes())
                  for sp in specs), x0.tobytes())
     cache = abc.__dict__.setdefault("_device_consts", {})
     if key not in cache:
         dev = gpu.require_device()
         cache.clear()
-        cache[key] = ([gpu.as_dev(sp[0], dtype=gpu.torch.int32, device=dev)
+        cache[key] = ([None if sp is None else
+                       gpu.as_dev(sp[0], dtype=gpu.torch.int32, device=dev)
                        for sp in specs],
-                      [gpu.as_dev(sp[1], device=dev) for sp in specs],
+                      [None if sp is None else gpu.as_dev(sp[1], device=dev)
+                       for sp in specs],
                       gpu.as_dev(x0, device=dev))
     return cache[key]
 
@@ -393,6 +456,7 @@ class ABCSMC:
         state = self.__dict__.copy()
         del state['sampler']
         state.pop("_device_consts", None)   # device tensors stay per process
+        state.pop("_grid_prior_dev", None)
         return state
 
     # -- history ------------------------------------------------------------
@@ -663,6 +727,8 @@ class ABCSMC:
         t0 = self.history.max_t + 1
         self.history.start_time = datetime.datetime.now()
         self.__dict__.pop("_prior_spec_cache", None)
+        self.__dict__.pop("_grid_spec_cache", None)
+        self.__dict__.pop("_grid_prior_dev", None)
         self._fit_transitions(t0)
         self._adapt_population_size(t0)
         self._initialize_dist_eps_acc(t0)
@@ -834,7 +900,10 @@ class ABCSMC:
             keep = ~gave_up
             theta, dist, key = theta[keep], dist[keep], key[keep]
             anc = None if anc is None else anc[keep]
-        if t - 1 == 0:
+        if t - 1 == 0 and _prior_specs(self)[0][0] is None:
+            # a grid prior proposed them
+            lp_prev = _grid_prior_device(self).logpmf_rows(theta)
+        elif t - 1 == 0:
             kinds, params, _ = _device_constants(self)
             lp_prev = gpu.prior_logpdf(theta, kinds[0], params[0])
             hl = host_prior_logpdf(theta, _prior_specs(self)[0][1])
