@@ -17,21 +17,10 @@
 // (diag(|X[0]|) for an all-zero covariance, scaling, "while det <= 0: cov +=
 // EPS I") and writes cov, inverse (Gauss-Jordan with partial pivoting), det
 // (LU), Cholesky and log normalisation.
-#include "abc_common.h"
+#include "abc_density.h"
 
 namespace abc {
-// direct-difference density for a runtime d (abc_local_wide.hip): d > 16, and
-// behind the MFMA route at d <= 16 for the candidates local_pdf_direct(uv,
-// tmax) names
-int local_wide_logpdf(const double* x, int64_t M, const double* X, const double* w,
-                      int64_t N, int d, const double* inv, const double* lnorm,
-                      double* out, hipStream_t s, const double* uv = nullptr,
-                      double tmax = 0.0);
 namespace {
-
-constexpr double LOG_2PI = 1.8378770664093454836;
-constexpr double LOG2E_L = 1.4426950408889634074;
-constexpr double LN2_L = 0.69314718055994530942;
 
 // squared distance with explicit fma: the select and accumulate kernels must
 // produce bit-identical keys
@@ -751,18 +740,6 @@ __global__ __launch_bounds__(256) void local_finish_kernel(
   m2 *= scaling;
   if (fired > 0 || (1.0 + m2) * F64_EPS > LOCAL_OFFCENTRE_LOSS || m2 < 0.0)
     queue[atomicAdd(qcount, 1)] = (int)n;
-}
-
-// sum of one value per thread over a block of 256, fixed tree (deterministic)
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  return sh[0];
 }
 
 // The queued particles' second pass, one block per particle (blocks stride
@@ -1607,7 +1584,7 @@ __global__ __launch_bounds__(256) void local_pack_kernel(
       const double c = (wj > 0.0) ? log(wj) - lnorm[j] : -INFINITY;
       v = c - 0.5 * qf;
     }
-    v *= LOG2E_L;
+    v *= LOG2E;
   }
   psi[e] = v;
 }
@@ -1754,7 +1731,7 @@ __global__ __launch_bounds__(256) void local_combine_kernel(
       const double2 p = part[(int64_t)c * M + i];
       if (p.x > -INFINITY) l += p.y * exp2(p.x - m);
     }
-  out[i] = (l > 0.0) ? LN2_L * (m + log2(l)) - log(wsum[0]) : -INFINITY;
+  out[i] = (l > 0.0) ? LN2 * (m + log2(l)) - log(wsum[0]) : -INFINITY;
 }
 
 // population tiles and their chunks (the launch grid's y)
@@ -1827,12 +1804,6 @@ int launch_pdf(const double* x, int64_t M, const double* X, const double* w,
 
 // the dimensions the fit and density kernels above are instantiated for
 using LocalDims = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
-
-// d > 16: runtime-d kernels (abc_local_wide.hip)
-size_t local_wide_fit_workspace(int64_t N, int d);
-int local_wide_fit(const double* X, const double* w, int64_t N, int d, int64_t nq,
-                   double scaling, double eps, double* covs, double* invs, double* dets,
-                   double* chol, double* lnorm, void* ws, size_t ws_bytes, hipStream_t s);
 }  // namespace abc
 
 using namespace abc;

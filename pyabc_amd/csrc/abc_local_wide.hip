@@ -28,13 +28,12 @@
 //      det and inverse from the same factors, as abc_local.hip), Cholesky.
 // pdf: one thread per candidate, population rows (inverse, row, log w -
 // log norm) staged in LDS and shared by the block, online log-sum-exp.
-#include "abc_common.h"
+#include "abc_density.h"
 
 namespace abc {
 namespace {
 
-constexpr double LOG_2PI_W = 1.8378770664093454836;
-constexpr int WT = 256;        // threads per workgroup
+constexpr int WT = 256;        // threads per workgroup (block_sum256)
 constexpr int WD_MAX = 64;
 constexpr int WCH = 32;        // member rows per LDS chunk (moments)
 
@@ -353,7 +352,7 @@ __global__ __launch_bounds__(WT) void local_wide_fit_kernel(WideFitArgs A) {
           L[a * d + b] = ok ? a_lu[(a) * ld + (b)] : ((a == b) ? sqrt(fabs(cov[(a) * ld + (a)])) : 0.0);
         }
       A.dets[n] = det;
-      A.lnorm[n] = 0.5 * (d * LOG_2PI_W + log(det));
+      A.lnorm[n] = 0.5 * (d * LOG_2PI + log(det));
     }
     __syncthreads();
   }
@@ -383,18 +382,12 @@ __global__ __launch_bounds__(WT) void local_wide_pdf_big_kernel(
       qf = __builtin_fma(Xj[a] - xi[a], y, qf);
     }
     const double s = (wj > 0.0 ? log(wj) : -INFINITY) - lnorm[j] - 0.5 * qf;
-    if (s > m) { l = l * exp(m - s) + 1.0; m = s; }
-    else if (s > -INFINITY) l += exp(s - m);
+    if (s > -INFINITY) lse_add<BaseE>(s, m, l);
   }
   double sw = 0.0;
   for (int64_t j = t; j < N; j += WT) sw += w[j];
-  wsum_sh[t] = sw;
-  __syncthreads();
-  for (int o = WT / 2; o > 0; o >>= 1) {
-    if (t < o) wsum_sh[t] += wsum_sh[t + o];
-    __syncthreads();
-  }
-  if (i < M) out[i] = (l > 0.0) ? m + log(l) - log(wsum_sh[0]) : -INFINITY;
+  sw = block_sum256(sw, wsum_sh);
+  if (i < M) out[i] = (l > 0.0) ? m + log(l) - log(sw) : -INFINITY;
 }
 
 // log density of candidate i: log sum_j w_j exp(-q_ij / 2) / norm_j - log sum w
@@ -444,21 +437,15 @@ __global__ __launch_bounds__(WT) void local_wide_pdf_kernel(
         qf = __builtin_fma(dl[a], y, qf);
       }
       const double s = sc[r] - 0.5 * qf;
-      if (s > m) { l = l * exp(m - s) + 1.0; m = s; }
-      else if (s > -INFINITY) l += exp(s - m);
+      if (s > -INFINITY) lse_add<BaseE>(s, m, l);
     }
     __syncthreads();
   }
   // np.average's denominator, fixed order per thread then a tree
   double sw = 0.0;
   for (int64_t j = t; j < N; j += WT) sw += w[j];
-  wsum_sh[t] = sw;
-  __syncthreads();
-  for (int o = WT / 2; o > 0; o >>= 1) {
-    if (t < o) wsum_sh[t] += wsum_sh[t + o];
-    __syncthreads();
-  }
-  if (i < M && mine) out[i] = (l > 0.0) ? m + log(l) - log(wsum_sh[0]) : -INFINITY;
+  sw = block_sum256(sw, wsum_sh);
+  if (i < M && mine) out[i] = (l > 0.0) ? m + log(l) - log(sw) : -INFINITY;
 }
 
 int wide_fit_blocks(int64_t N, int d) {

@@ -21,13 +21,11 @@
 // directly; m starts at |z|^2 log2e / 2, which bounds s - m above by
 // log2(max w e^shift), and a rare wave-uniform branch re-centres m when a
 // value would overflow (> 2^64) or every value so far underflowed.
-#include "abc_common.h"
+#include "abc_density.h"
 
 namespace abc {
 namespace {
 
-constexpr double LOG2E = 1.4426950408889634074;
-constexpr double LN2 = 0.69314718055994530942;
 constexpr float THR_HI = 64.f;   // re-centre if s - m exceeds this (log2)
 constexpr float THR_LO = -64.f;  // ... or if nothing accumulated and below
 
@@ -49,8 +47,7 @@ template <> struct Acc<double> {
 };
 
 // ---- packing ---------------------------------------------------------------
-// A image: packed[t][lane][kb], t = 16-row population tile, lane 0..63,
-// kb = 0..KB-1; element (row 16t + (lane & 15), k = 4 kb + (lane >> 4)).
+// A image (operand_at) of the whitened population, column r = log2e c_j
 template <class T>
 __global__ void pack_population_kernel(const double* __restrict__ X,
                                        const double* __restrict__ w, int64_t N,
@@ -66,9 +63,7 @@ __global__ void pack_population_kernel(const double* __restrict__ X,
   if (row < N) {
     double y2 = 0.0;
     for (int k = 0; k < r; ++k) {
-      double acc = 0.0;
-      for (int q = 0; q < d; ++q) acc += (X[row * d + q] - mu[q]) * U[q * r + k];
-      T yt = (T)acc;          // the operand the MFMA will see
+      T yt = (T)whiten_row(X + row * d, mu, U, d, r, k);   // the operand the MFMA will see
       yv[k] = yt;
       y2 += (double)yt * (double)yt;
     }
@@ -78,13 +73,9 @@ __global__ void pack_population_kernel(const double* __restrict__ X,
     for (int k = 0; k < r; ++k) yv[k] = (T)0;
     c = -INFINITY;
   }
-  int64_t t = row >> 4;
-  int rl = (int)(row & 15);
-  for (int k = 0; k < K; ++k) {
-    T v = (k < r) ? yv[k] : (k == r ? (T)c : (T)0);
-    int kb = k >> 2, lane = rl + 16 * (k & 3);
-    packed[(t * 64 + lane) * KB + kb] = v;
-  }
+  for (int k = 0; k < K; ++k)
+    packed[operand_at(row >> 4, (int)(row & 15), k, KB)] =
+        (k < r) ? yv[k] : (k == r ? (T)c : (T)0);
 }
 
 // B image for candidates + per-candidate m0 = |u|^2 log2e / 2 (fp64), where
@@ -102,9 +93,7 @@ __global__ void pack_candidates_kernel(const double* __restrict__ x, int64_t M,
   double b2 = 0.0;
   if (col < M) {
     for (int k = 0; k < r; ++k) {
-      double acc = 0.0;
-      for (int q = 0; q < d; ++q) acc += (x[col * d + q] - mu[q]) * U[q * r + k];
-      T bt = (T)(acc * LOG2E);
+      T bt = (T)(whiten_row(x + col * d, mu, U, d, r, k) * LOG2E);
       bv[k] = bt;
       b2 += (double)bt * (double)bt;
     }
@@ -112,13 +101,9 @@ __global__ void pack_candidates_kernel(const double* __restrict__ x, int64_t M,
   } else {
     for (int k = 0; k < r; ++k) bv[k] = (T)0;
   }
-  int64_t t = col >> 4;
-  int cl = (int)(col & 15);
-  for (int k = 0; k < K; ++k) {
-    T v = (k < r) ? bv[k] : (k == r ? (T)1 : (T)0);
-    int kb = k >> 2, lane = cl + 16 * (k & 3);
-    packed[(t * 64 + lane) * KB + kb] = v;
-  }
+  for (int k = 0; k < K; ++k)
+    packed[operand_at(col >> 4, (int)(col & 15), k, KB)] =
+        (k < r) ? bv[k] : (k == r ? (T)1 : (T)0);
 }
 
 // ---- the fused cross-term GEMM + exp2 + log-sum-exp -----------------------
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(256) void mvn_lse_kernel(
     const bool live = ct < MT;
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
-      b[c][kb] = live ? Bp[(ct * 64 + lane) * KB + kb] : (T)0;
+      b[c][kb] = live ? Bp[operand_lane_at(ct, lane, kb, KB)] : (T)0;
     const int64_t cand = ct * 16 + (lane & 15);
     m[c] = live ? (T)m0[cand] : (T)0;
     l[c] = 0.0;
@@ -164,12 +149,12 @@ __global__ __launch_bounds__(256) void mvn_lse_kernel(
   T a[KB], an[KB];
   if (t_begin < t_end) {
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) a[kb] = A[(t_begin * 64 + lane) * KB + kb];
+    for (int kb = 0; kb < KB; ++kb) a[kb] = A[operand_lane_at(t_begin, lane, kb, KB)];
   }
   for (int64_t t = t_begin; t < t_end; ++t) {
     const int64_t tn = (t + 1 < t_end) ? t + 1 : t;
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) an[kb] = A[(tn * 64 + lane) * KB + kb];
+    for (int kb = 0; kb < KB; ++kb) an[kb] = A[operand_lane_at(tn, lane, kb, KB)];
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       V acc = {-m[c], -m[c], -m[c], -m[c]};
@@ -217,13 +202,8 @@ __global__ __launch_bounds__(256) void mvn_lse_kernel(
     double mm = (double)m[c], ll = l[c];
 #pragma unroll
     for (int o = 16; o < 64; o <<= 1) {
-      double mo = __shfl_xor(mm, o, 64), lo = __shfl_xor(ll, o, 64);
-      double mx = fmax(mm, mo);
-      double s = 0.0;
-      if (ll > 0.0) s += ll * exp2(mm - mx);
-      if (lo > 0.0) s += lo * exp2(mo - mx);
-      mm = (ll > 0.0 || lo > 0.0) ? mx : mm;
-      ll = s;
+      const double mo = __shfl_xor(mm, o, 64), lo = __shfl_xor(ll, o, 64);
+      lse_merge<Base2>(mm, ll, mo, lo);
     }
     const int64_t ct = ct0 + c;
     if (lane < 16 && ct < MT) {
@@ -241,18 +221,8 @@ __global__ void mvn_combine_kernel(const double* __restrict__ part_m,
                                    double* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
-  double mx = -INFINITY;
-  for (int c = 0; c < nchunk; ++c) {
-    double lv = part_l[(int64_t)c * Mpad + i];
-    if (lv > 0.0) mx = fmax(mx, part_m[(int64_t)c * Mpad + i]);
-  }
-  if (mx == -INFINITY) { out[i] = -INFINITY; return; }
-  double s = 0.0;
-  for (int c = 0; c < nchunk; ++c) {
-    double lv = part_l[(int64_t)c * Mpad + i];
-    if (lv > 0.0) s += lv * exp2(part_m[(int64_t)c * Mpad + i] - mx);
-  }
-  out[i] = LN2 * (mx + log2(s) - m0[i]) + log_const;
+  const LsePair p = lse_combine<Base2>(part_m, part_l, Mpad, nchunk, i);
+  out[i] = p.m == -INFINITY ? -INFINITY : LN2 * (p.m + log2(p.l) - m0[i]) + log_const;
 }
 
 // ---- direct-difference fp64 VALU kernel (any rank, singular support) -------
@@ -261,7 +231,6 @@ __global__ __launch_bounds__(256) void mvn_direct_kernel(
     const double* __restrict__ w, int64_t N, int d,
     const double* __restrict__ U, int r, const double* __restrict__ V, int nv,
     double tol, double log_const, double* __restrict__ out) {
-  __shared__ double sm[4], sl[4];
   const int64_t i = blockIdx.x;
   if (i >= M) return;
   double xi[64];
@@ -289,32 +258,9 @@ __global__ __launch_bounds__(256) void mvn_direct_kernel(
       for (int q = 0; q < d; ++q) p += dev[q] * U[q * r + k];
       maha += p * p;
     }
-    double s = log(wj) - 0.5 * maha;
-    if (s > m) { l = l * exp(m - s) + 1.0; m = s; }
-    else l += exp(s - m);
+    lse_add<BaseE>(log(wj) - 0.5 * maha, m, l);
   }
-  // wave reduce (m, l)
-  for (int o = 32; o > 0; o >>= 1) {
-    double mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
-    double mx = fmax(m, mo);
-    double s = 0.0;
-    if (l > 0.0) s += l * exp(m - mx);
-    if (lo > 0.0) s += lo * exp(mo - mx);
-    m = (l > 0.0 || lo > 0.0) ? mx : m;
-    l = s;
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wv] = m; sl[wv] = l; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double mx = -INFINITY;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k)
-      if (sl[k] > 0.0) mx = fmax(mx, sm[k]);
-    double s = 0.0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k)
-      if (sl[k] > 0.0) s += sl[k] * exp(sm[k] - mx);
-    out[i] = (s > 0.0) ? mx + log(s) + log_const : -INFINITY;
-  }
+  direct_finish(m, l, log_const, out + i);
 }
 
 // d > 64: the candidate row in LDS (dynamic, d doubles), the differences
@@ -326,7 +272,6 @@ __global__ __launch_bounds__(256) void mvn_direct_wide_kernel(
     const double* __restrict__ U, int r, const double* __restrict__ V, int nv,
     double tol, double log_const, double* __restrict__ out) {
   extern __shared__ double xs[];
-  __shared__ double sm[4], sl[4];
   const int64_t i = blockIdx.x;
   if (i >= M) return;
   for (int q = threadIdx.x; q < d; q += blockDim.x) xs[q] = x[i * d + q];
@@ -351,57 +296,23 @@ __global__ __launch_bounds__(256) void mvn_direct_wide_kernel(
       for (int q = 0; q < d; ++q) p += (xs[q] - Xj[q]) * U[q * r + k];
       maha += p * p;
     }
-    const double s = log(wj) - 0.5 * maha;
-    if (s > m) { l = l * exp(m - s) + 1.0; m = s; }
-    else l += exp(s - m);
+    lse_add<BaseE>(log(wj) - 0.5 * maha, m, l);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    double mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
-    double mx = fmax(m, mo);
-    double s = 0.0;
-    if (l > 0.0) s += l * exp(m - mx);
-    if (lo > 0.0) s += lo * exp(mo - mx);
-    m = (l > 0.0 || lo > 0.0) ? mx : m;
-    l = s;
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wv] = m; sl[wv] = l; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double mx = -INFINITY;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k)
-      if (sl[k] > 0.0) mx = fmax(mx, sm[k]);
-    double s = 0.0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k)
-      if (sl[k] > 0.0) s += sl[k] * exp(sm[k] - mx);
-    out[i] = (s > 0.0) ? mx + log(s) + log_const : -INFINITY;
-  }
+  direct_finish(m, l, log_const, out + i);
 }
 
-struct Plan {
-  int KB, CT, nchunk;
-  int64_t MT, NT, MTpad, groups, tiles_per_chunk, Mpad;
+struct Plan : TilePlan {
+  int KB, nchunk;
+  int64_t tiles_per_chunk;
   size_t esize;
 };
 
 Plan make_plan(int64_t M, int64_t N, int r, int prec) {
   Plan p;
+  static_cast<TilePlan&>(p) = tile_plan(M, N, 4);   // launch_lse: CT = 4
   p.KB = (int)ceil_div(r + 1, 4);
-  p.CT = 4;
   p.esize = prec == ABC_PREC_F32 ? 4 : 8;
-  p.MT = ceil_div(M > 0 ? M : 1, 16);
-  p.NT = ceil_div(N > 0 ? N : 1, 16);
-  const int64_t waves = ceil_div(p.MT, p.CT);
-  p.groups = ceil_div(waves, 4);
-  p.MTpad = p.groups * 4 * p.CT;
-  p.Mpad = p.MTpad * 16;
-  // enough waves to fill 256 CUs several times over, chunks >= 32 tiles
-  int64_t want = ceil_div(16384, p.groups * 4);
-  int64_t maxc = ceil_div(p.NT, 32);
-  int64_t nc = want < maxc ? want : maxc;
-  nc = ceil_div(nc < 1 ? 1 : nc, 8) * 8;  // multiple of 8 for the XCD map
-  if (nc > 1024) nc = 1024;
-  p.nchunk = (int)nc;
+  p.nchunk = (int)(ceil_div(p.nc, 8) * 8);   // multiple of 8 for the XCD map (1024 is one)
   p.tiles_per_chunk = ceil_div(p.NT, p.nchunk);
   return p;
 }
@@ -437,22 +348,6 @@ int dispatch_lse(const Plan& p, const T* A, const T* B, const double* m0,
 }
 
 }  // namespace
-}  // namespace abc
-
-namespace abc {
-size_t x3_packed_bytes(int64_t N, int r);
-int x3_max_rank();
-int x3_pack_population(const double* X, const double* w, int64_t N, int d,
-                       const double* mu, const double* U, int r,
-                       double log_w_shift, const double* shift_dev, void* packed,
-                       double* range, hipStream_t s);
-size_t x3_logpdf_workspace(int64_t M, int64_t N, int r);
-int x3_logpdf(const double* x, int64_t M, int d, const void* packed,
-              const double* X, const double* w, int64_t N, const double* mu,
-              const double* U, int r, double log_const, double log_norm,
-              double* out, const int64_t* hint, void* ws, size_t ws_bytes,
-              hipStream_t s, int prof_channel = ABC_PROF_DENSITY,
-              const unsigned int* count_dev = nullptr);
 }  // namespace abc
 
 using namespace abc;

@@ -28,13 +28,11 @@
 // there; a term 2^-k below the largest weighs 2^-k in the sum).  A held-out
 // point many kernel widths from every train row is then finite wherever the
 // fp64 value is.
-#include "abc_common.h"
+#include "abc_density.h"
 
 namespace abc {
 namespace {
 
-constexpr double LOG2E = 1.4426950408889634074;
-constexpr double LN2 = 0.69314718055994530942;
 constexpr float THR_HI = 2.f;     // move m_g if an exponent exceeds this (log2)
 constexpr float THR_LO = -2.f;    // ... or if nothing accumulated and below
 // ln 2^-1075: below it every term w_j pdf_j of the reference's fp64 sum has
@@ -49,10 +47,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 struct Scales { double inv[GCAP]; };
 struct Consts { double c[GMAX]; };
 
-// A image: packed[t][lane][kb], element (row 16t + (lane & 15), k = 4 kb +
-// (lane >> 4)); column r holds -log2e |y|^2 / 2.  lw[t][lane >> 4][v] =
-// log2 w of row 16t + (lane >> 4) + 4v, the row of the f64 MFMA's result v in
-// that lane (-inf for w = 0 and for the padding rows).
+// A image (operand_at); column r holds -log2e |y|^2 / 2.  lw[t][lane >> 4][v]
+// = log2 w of row 16t + (lane >> 4) + 4v, the row of the f64 MFMA's result v
+// in that lane (-inf for w = 0 and for the padding rows).
 __global__ void scaled_pack_population(const double* __restrict__ X,
                                        const double* __restrict__ w, int64_t N,
                                        int d, const double* __restrict__ mu,
@@ -68,8 +65,7 @@ __global__ void scaled_pack_population(const double* __restrict__ X,
   if (row < N) {
     double y2 = 0.0;
     for (int k = 0; k < r; ++k) {
-      double acc = 0.0;
-      for (int q = 0; q < d; ++q) acc += (X[row * d + q] - mu[q]) * U[q * r + k];
+      const double acc = whiten_row(X + row * d, mu, U, d, r, k);
       yv[k] = acc;
       y2 += acc * acc;
     }
@@ -79,11 +75,8 @@ __global__ void scaled_pack_population(const double* __restrict__ X,
   }
   const int64_t t = row >> 4;
   const int rl = (int)(row & 15);
-  for (int k = 0; k < K; ++k) {
-    const double v = (k < r) ? yv[k] : (k == r ? aug : 0.0);
-    const int kb = k >> 2, lane = rl + 16 * (k & 3);
-    packed[(t * 64 + lane) * KB + kb] = v;
-  }
+  for (int k = 0; k < K; ++k)
+    packed[operand_at(t, rl, k, KB)] = (k < r) ? yv[k] : (k == r ? aug : 0.0);
   lw[t * 16 + (rl & 3) * 4 + (rl >> 2)] = l2w;
 }
 
@@ -102,21 +95,15 @@ __global__ void scaled_pack_points(const double* __restrict__ x, int64_t M, int 
   for (int k = 0; k < r; ++k) bv[k] = 0.0;
   if (col < M) {
     for (int k = 0; k < r; ++k) {
-      double acc = 0.0;
-      for (int q = 0; q < d; ++q) acc += (x[col * d + q] - mu[q]) * U[q * r + k];
-      const double bt = acc * LOG2E;
+      const double bt = whiten_row(x + col * d, mu, U, d, r, k) * LOG2E;
       bv[k] = bt;
       b2 += bt * bt;
     }
   }
   z0[col] = -0.5 * b2 / LOG2E;
-  const int64_t t = col >> 4;
-  const int cl = (int)(col & 15);
-  for (int k = 0; k < K; ++k) {
-    const double v = (k < r) ? bv[k] : (k == r ? 1.0 : 0.0);
-    const int kb = k >> 2, lane = cl + 16 * (k & 3);
-    packed[(t * 64 + lane) * KB + kb] = v;
-  }
+  for (int k = 0; k < K; ++k)
+    packed[operand_at(col >> 4, (int)(col & 15), k, KB)] =
+        (k < r) ? bv[k] : (k == r ? 1.0 : 0.0);
 }
 
 // One wave = CT point tiles x one population chunk x GT grid points; block =
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(256) void mvn_scaled_kernel(
     const bool live = ct < MT;
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
-      b[c][kb] = live ? Bp[(ct * 64 + lane) * KB + kb] : 0.0;
+      b[c][kb] = live ? Bp[operand_lane_at(ct, lane, kb, KB)] : 0.0;
     zc[c] = live ? z0[ct * 16 + (lane & 15)] : 0.0;
 #pragma unroll
     for (int g = 0; g < GT; ++g) { m[c][g] = 0.0; l[c][g] = 0.0; }
@@ -157,14 +144,14 @@ __global__ __launch_bounds__(256) void mvn_scaled_kernel(
   double wl[4], wn[4];
   if (t_begin < t_end) {
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) a[kb] = A[(t_begin * 64 + lane) * KB + kb];
+    for (int kb = 0; kb < KB; ++kb) a[kb] = A[operand_lane_at(t_begin, lane, kb, KB)];
 #pragma unroll
     for (int v = 0; v < 4; ++v) wl[v] = lw[t_begin * 16 + (lane >> 4) * 4 + v];
   }
   for (int64_t t = t_begin; t < t_end; ++t) {
     const int64_t tn = (t + 1 < t_end) ? t + 1 : t;
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) an[kb] = A[(tn * 64 + lane) * KB + kb];
+    for (int kb = 0; kb < KB; ++kb) an[kb] = A[operand_lane_at(tn, lane, kb, KB)];
 #pragma unroll
     for (int v = 0; v < 4; ++v) wn[v] = lw[tn * 16 + (lane >> 4) * 4 + v];
 #pragma unroll
@@ -213,15 +200,7 @@ __global__ __launch_bounds__(256) void mvn_scaled_kernel(
 #pragma unroll
       for (int o = 16; o < 64; o <<= 1) {
         const double mo = __shfl_xor(mm, o, 64), lo = __shfl_xor(ll, o, 64);
-        // a side that accumulated nothing (all its rows of weight zero) has
-        // no reference of its own: it must not raise the other side's
-        const bool ha = ll > 0.0, hb = lo > 0.0;
-        const double mx = (ha && hb) ? fmax(mm, mo) : (ha ? mm : mo);
-        double s = 0.0;
-        if (ha) s += ll * exp2(mm - mx);
-        if (hb) s += lo * exp2(mo - mx);
-        mm = mx;
-        ll = s;
+        lse_merge_live<Base2>(mm, ll, mo, lo);
       }
       const int64_t ct = ct0 + c;
       if (lane < 16 && ct < MT && g < greal) {
@@ -241,19 +220,11 @@ __global__ void scaled_combine_kernel(const double* __restrict__ part_m,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int g = blockIdx.y;
   if (i >= M) return;
-  const double* pm = part_m + (int64_t)g * nchunk * Mpad;
-  const double* pl = part_l + (int64_t)g * nchunk * Mpad;
-  double mx = -INFINITY;
-  for (int c = 0; c < nchunk; ++c)
-    if (pl[(int64_t)c * Mpad + i] > 0.0) mx = fmax(mx, pm[(int64_t)c * Mpad + i]);
+  const int64_t at = (int64_t)g * nchunk * Mpad;
+  const LsePair p = lse_combine<Base2>(part_m + at, part_l + at, Mpad, nchunk, i);
   double v = -INFINITY;
-  if (mx > -INFINITY) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) {
-      const double lv = pl[(int64_t)c * Mpad + i];
-      if (lv > 0.0) s += lv * exp2(pm[(int64_t)c * Mpad + i] - mx);
-    }
-    v = LN2 * (mx + log2(s)) + lc.c[g];
+  if (p.m > -INFINITY) {
+    v = LN2 * (p.m + log2(p.l)) + lc.c[g];
     if (v < LOG_F64_UNDERFLOW) v = -INFINITY;
   }
   out[(int64_t)g * M + i] = v;
@@ -300,27 +271,17 @@ int scaled_gt(int g) {
 
 // The decomposition depends on (M, N, r) only, never on G: a grid point's
 // result is the same bits whichever launch carries it.
-struct SPlan {
+struct SPlan : TilePlan {
   int KB, nchunk, G;
-  int64_t MT, NT, MTpad, groups, tiles_per_chunk, Mpad;
+  int64_t tiles_per_chunk;
 };
 
 SPlan make_splan(int64_t M, int64_t N, int r, int G) {
   SPlan p;
+  static_cast<TilePlan&>(p) = tile_plan(M, N, CT);
   p.KB = scaled_kb(r);
   p.G = G;
-  p.MT = ceil_div(M > 0 ? M : 1, 16);
-  p.NT = ceil_div(N > 0 ? N : 1, 16);
-  p.groups = ceil_div(ceil_div(p.MT, CT), 4);
-  p.MTpad = p.groups * 4 * CT;
-  p.Mpad = p.MTpad * 16;
-  // enough waves to fill 256 CUs several times over, chunks >= 32 tiles
-  const int64_t want = ceil_div(16384, p.groups * 4);
-  const int64_t maxc = ceil_div(p.NT, 32);
-  int64_t nc = want < maxc ? want : maxc;
-  if (nc < 1) nc = 1;
-  if (nc > 1024) nc = 1024;
-  p.tiles_per_chunk = ceil_div(p.NT, nc);
+  p.tiles_per_chunk = ceil_div(p.NT, p.nc);
   p.nchunk = (int)ceil_div(p.NT, p.tiles_per_chunk);   // no empty chunk
   return p;
 }

@@ -73,7 +73,7 @@
 // underflows 2^-60 relative to max w (all pairs beyond ~11 kernel widths),
 // are recomputed in fp64 from the whitened population Y and log2 weights lw
 // stored after the fragments (rescue list; empty in practice).
-#include "abc_common.h"
+#include "abc_density.h"
 
 namespace abc {
 namespace {
@@ -81,9 +81,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr double LOG2E = 1.4426950408889634074;
 constexpr double SQRT_LOG2E = 1.2011224087864498;  // sqrt(log2 e)
-constexpr double LN2 = 0.69314718055994530942;
 constexpr int MAX_R = 25;       // exact groups r + 7 <= 32
 // E_MAX: the largest exponent at which every rank meets the contract (header);
 // the host reads it through abc_mvn_x3_max_exponent
@@ -705,12 +703,9 @@ __global__ void x3_combine_kernel(const double* __restrict__ part_o,
     om = (double)cand_o[i];
     for (int c = 0; c < nchunk; ++c) s += part_l[(int64_t)c * Mpad + i];
   } else {
-    for (int c = 0; c < nchunk; ++c)
-      if (part_l[(int64_t)c * Mpad + i] > 0.0) om = fmax(om, part_o[(int64_t)c * Mpad + i]);
-    for (int c = 0; c < nchunk; ++c) {
-      const double l = part_l[(int64_t)c * Mpad + i];
-      if (l > 0.0) s += l * exp2(part_o[(int64_t)c * Mpad + i] - om);
-    }
+    const LsePair p = lse_combine<Base2>(part_o, part_l, Mpad, nchunk, i);
+    om = p.m;
+    s = p.l;
   }
   const double lg = om + log2(s);  // log2 of sum_j 2^s_ij
   // below 2^-60 (relative to max w) terms flushed at the f32 exp2 floor
@@ -769,11 +764,6 @@ __global__ __launch_bounds__(256) void x3_combine_rows_kernel(
 // candidate with many comparable terms 2e-8 out in log density (measured:
 // N = 500, d = 5, candidates beside their ancestors), where its callers
 // promise fp64.  The list is empty or a handful of rows in practice.
-__device__ __forceinline__ void online_add(double s, double& m, double& l) {
-  const double dl = s - m;
-  if (dl > 0.0) { l = l * exp2(-dl) + 1.0; m = s; }
-  else l += exp2(dl);
-}
 
 // Rescue v2: one rescued candidate per lane with its whitened coordinates
 // in registers; the population is cut in RS slices that depend on N only
@@ -814,11 +804,7 @@ __global__ __launch_bounds__(64) void x3_rescue_kernel(
     const int64_t i = act ? rescue[q0 + q] : 0;
 #pragma unroll
     for (int k = 0; k < MAX_R; ++k) {
-      if (k < r) {
-        double acc = 0.0;
-        for (int cc = 0; cc < d; ++cc) acc += (x[i * d + cc] - mu[cc]) * U[cc * r + k];
-        z[k] = acc * SQRT_LOG2E;
-      }
+      if (k < r) z[k] = whiten_row(x + i * d, mu, U, d, r, k) * SQRT_LOG2E;
     }
     double m = -INFINITY, l = 0.0;
     for (int64_t jt = j0; jt < j1; jt += 64) {
@@ -838,7 +824,7 @@ __global__ __launch_bounds__(64) void x3_rescue_kernel(
             q2 = fma(dz, dz, q2);
           }
         }
-        online_add(lwj - 0.5 * q2, m, l);
+        lse_add<Base2>(lwj - 0.5 * q2, m, l);
       }
     }
     if (act) {
@@ -856,15 +842,8 @@ __global__ void x3_rescue_final(const int64_t* __restrict__ rescue,
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = (int64_t)*nrescue;
   if (q >= cap || q0 + q >= n) return;
-  double mx = -INFINITY;
-  for (int c = 0; c < nslice; ++c)
-    if (pl[(int64_t)c * cap + q] > 0.0) mx = fmax(mx, pm[(int64_t)c * cap + q]);
-  double t = 0.0;
-  for (int c = 0; c < nslice; ++c) {
-    const double l = pl[(int64_t)c * cap + q];
-    if (l > 0.0) t += l * exp2(pm[(int64_t)c * cap + q] - mx);
-  }
-  out[rescue[q0 + q]] = t > 0.0 ? log_const + LN2 * (mx + log2(t)) : -INFINITY;
+  const LsePair p = lse_combine<Base2>(pm, pl, cap, nslice, q);
+  out[rescue[q0 + q]] = p.l > 0.0 ? log_const + LN2 * (p.m + log2(p.l)) : -INFINITY;
 }
 
 // ranks pack_x3_kernel is instantiated for; any other r runs its runtime-r

@@ -56,6 +56,58 @@ def test_mvn_pdf_golden(dev, tag, precision, rtol):
     np.testing.assert_allclose(pdf, gg["pdf"], rtol=rtol, atol=0)
 
 
+def _lane_group_case(M, N, d, zero, far):
+    """Population, weights (zero on the rows `zero` names), a whitening of a
+    fixed covariance and M candidates: on the population, near it and, with
+    `far`, one 30 whitened units from the nearest row."""
+    rng = np.random.default_rng(1000 * N + d)
+    A = rng.standard_normal((d, d)) + 2.0 * np.eye(d)
+    cov = A @ A.T
+    L = np.linalg.cholesky(cov)
+    U = np.linalg.inv(L).T                    # U U^T = cov^-1, |(x - X) U| the whitened distance
+    mu = rng.standard_normal(d)
+    X = mu + rng.standard_normal((N, d)) @ L.T
+    w = np.exp(0.5 * rng.standard_normal(N))
+    w[[j for j in range(N) if zero(j)]] = 0.0
+    w /= w.sum()
+    anc = X[rng.integers(0, N, M)]
+    x = anc + 0.3 * rng.standard_normal((M, d)) @ L.T
+    x[:M // 3] = anc[:M // 3]
+    if far:
+        e = np.zeros(d)
+        e[0] = ((X - mu) @ U)[:, 0].max() + 30.0     # 30 past the outermost row
+        x[-1] = mu + L @ e
+    return X, w, mu, U, cov, x
+
+
+@pytest.mark.parametrize("prec,atol", [("f64", 2e-6), ("f32", 1e-4)])
+@pytest.mark.parametrize("M,N,d,zero", [
+    (17, 1, 2, lambda j: False), (17, 2, 2, lambda j: False), (17, 3, 2, lambda j: False),
+    (33, 130, 3, lambda j: j % 4 == 2), (33, 130, 3, lambda j: 8 <= j % 16 < 12)],
+    ids=["N1", "N2", "N3", "zero_f64_group", "zero_f32_group"])
+def test_mvn_logpdf_empty_lane_group(dev, M, N, d, zero, prec, atol):
+    """abc_mvn_pack_population + abc_mvn_logpdf with a lane group of the MFMA
+    result that accumulates nothing: tiles short of 16 rows (N = 1, 2, 3),
+    and weight zero on the rows one group owns in every tile (rows = 2 mod 4
+    in the f64 result layout, rows 8..11 of 16 in the f32 one).  The group's
+    pair stays empty with its reference at the start value; the lane merge
+    must not read it as a term.  In f64 a candidate 30 whitened units out
+    (log density about -450, above the fp64 floor -745) pulls the live
+    groups' reference ~650 log2 units below that start.  Absolute error of
+    the log density: 2e-6 (f64), 1e-4 (f32), this file's figures."""
+    from pyabc_amd import gpu
+    from pyabc_amd import _native as nat
+    X, w, mu, U, cov, x = _lane_group_case(M, N, d, zero, far=prec == "f64")
+    ref = oracle.transition.mvn_logpdf(x, X, w, cov)
+    assert np.isfinite(ref).all()
+    p = {"f64": nat.ABC_PREC_F64, "f32": nat.ABC_PREC_F32}[prec]
+    shift = np.log(N)
+    log_norm = -0.5 * (d * np.log(2 * np.pi) + np.linalg.slogdet(cov)[1])
+    packed = gpu.mvn_pack(T(X), T(w), T(mu), T(U), shift, p)
+    got = gpu.mvn_logpdf(T(x), packed, N, T(mu), T(U), p, log_norm - shift).cpu().numpy()
+    np.testing.assert_allclose(got, ref, rtol=0, atol=atol)
+
+
 @pytest.mark.parametrize("d,rule,rank,tiny", [(1, 0, 1, 1), (2, 1, 2, 1), (10, 0, 10, 1),
                                               (10, 0, 7, 1), (25, 1, 25, 1), (40, 0, 40, 1),
                                               (64, 0, 64, 1), (6, 0, 6, 1e-7), (8, 1, 8, 3e-4),
