@@ -892,6 +892,54 @@ int abc_walk_logpmf(const double* x, int64_t M, const int32_t* Xi,
                     int n_steps, double* out, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* ---- marginal KDE panels on their plot grids (abc_kde.hip) ----------------
+ * kde_1d / kde_2d (pyabc/visualization/kde.py:19-74, 174-248) for P panels
+ * of one population at once: panel p is MultivariateNormalTransition.fit on
+ * one or two columns of X followed by .pdf on a linspace / meshgrid grid.
+ * The host plans the panels (every covariance is a sub-block of the one
+ * d x d covariance) and hands over, per panel, a host struct:
+ *   col     the column(s) of X; col[1] = -1 for a 1-D panel
+ *   num     numx, numy (numy = 1 for a 1-D panel), each in [1, 4096]
+ *   axis    offsets of the panel's x and y coordinates in coords (device
+ *           float64 [n_coords]: the host's own linspace values)
+ *   centre  subtracted from columns and coordinates before whitening
+ *   U       2 x 2 row major, U U^T = Sigma^-1: z = (x - centre) U; a 1-D
+ *           panel reads U[0] alone
+ *   log_const  -(k log 2 pi + log det Sigma) / 2
+ *   out     offset of the panel's densities in out; the panels lie back to
+ *           back in descriptor order (out_0 = 0, out_p+1 = out_p + numx numy)
+ * out [G_total] = log sum_j w_j N(g - X_j; Sigma_p) in meshgrid order
+ * (index iy numx + ix).  A particle of weight 0 contributes nothing; every
+ * sum follows its largest term, so none underflows: far from the population
+ * the result is a large negative number, and -inf only where no particle has
+ * weight.  A NaN coordinate or weight gives NaN.
+ * Arithmetic: differences, the whitened quadratic form and the exponent in
+ * fp64; the exp2 in fp32 of the exponent's fraction beside a running fp64
+ * reference; sums as (m, l) pairs.  The population is cut into chunks (a
+ * function of N and G_total alone), each (tile of 512 grid points, chunk)
+ * sums its rows in ascending order and a finishing launch combines the
+ * chunks in ascending order: no atomics, the same bits on every call.
+ * Caps (ABC_ERR_UNSUPPORTED beyond them; the size query returns 0):
+ * d <= 64, P <= ABC_KDE_MAX_PANELS, G_total <= 2^24.  The call uploads the
+ * descriptors and waits for that copy on the stream. */
+#define ABC_KDE_MAX_PANELS 2080
+#define ABC_KDE_MAX_AXIS 4096
+#define ABC_KDE_MAX_POINTS (1 << 24)
+typedef struct abc_kde_panel {
+  int col[2];
+  int num[2];
+  int64_t axis[2];
+  double centre[2];
+  double U[4];
+  double log_const;
+  int64_t out;
+} abc_kde_panel;
+size_t abc_kde_panels_bytes(int64_t N, int d, int P, int64_t G_total);
+int abc_kde_panels(const double* X, const double* w, int64_t N, int d,
+                   const abc_kde_panel* panels, int P, const double* coords,
+                   int64_t n_coords, double* out, int64_t G_total, void* ws,
+                   size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

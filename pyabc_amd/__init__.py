@@ -45,6 +45,7 @@ from .populationstrategy import (ConstantPopulationSize, PopulationStrategy,
 from .weighted_statistics import (weighted_quantile, weighted_median,
                                   weighted_mean, weighted_std,
                                   effective_sample_size)
+from . import visualization
 
 __version__ = "0.1.0"
 

@@ -125,6 +125,8 @@ SIGNATURES = {
     "abc_walk_logpmf_chunk": (I64, [I64, I64, I32]),
     "abc_walk_logpmf_bytes": (SZ, [I64, I64, I32]),
     "abc_walk_logpmf": (I32, [P, I64, P, P, I64, I32, P, I32, P, P, SZ, P]),
+    "abc_kde_panels_bytes": (SZ, [I64, I32, I32, I64]),
+    "abc_kde_panels": (I32, [P, P, I64, I32, P, I32, P, I64, P, I64, P, SZ, P]),
 }
 
 
@@ -153,6 +155,15 @@ class GridPrior(C.Structure):
     _fields_ = [("d", C.c_int), ("coord", P), ("logpmf", P), ("cdf", P)]
 
 
+class KdePanel(C.Structure):
+    """abc_kde_panel (include/abcgpu.h), field for field."""
+    _fields_ = [("col", C.c_int * 2), ("num", C.c_int * 2), ("axis", I64 * 2),
+                ("centre", D * 2), ("U", D * 4), ("log_const", D), ("out", I64)]
+
+
+ABC_KDE_MAX_PANELS = 2080
+ABC_KDE_MAX_AXIS = 4096
+ABC_KDE_MAX_POINTS = 1 << 24
 ABC_MODELS_MAX = 16
 ABC_WALK_MAX_D = 32
 ABC_WALK_MAX_STEPS = 512

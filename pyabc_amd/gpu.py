@@ -304,6 +304,35 @@ def mvn_logpdf_scaled(xd, Xd, wd, mu, U, scalings, log_consts, wt=None):
     return out, score
 
 
+def kde_panels_bytes(N, d, P, G_total):
+    """abc_kde_panels' workspace for that shape; 0 beyond the entry's caps."""
+    return nat.query("abc_kde_panels_bytes", int(N), int(d), int(P), int(G_total))
+
+
+def kde_panels(X, w, panels, coords):
+    """Marginal KDEs of the population (X [N, d], w [N], device) on their grids
+    in one pass (abc_kde_panels) -> device log densities [sum numx numy],
+    panel after panel in meshgrid order.  panels: a ctypes array of
+    nat.KdePanel (visualization.plan_panels(...).descriptors()); coords: the
+    host float64 axis coordinates the descriptors' offsets point into."""
+    import ctypes
+    N, d = X.shape
+    P = len(panels)
+    G_total = sum(int(q.num[0]) * int(q.num[1]) for q in panels)
+    coords = np.ascontiguousarray(coords, dtype=np.float64).ravel()
+    nb = kde_panels_bytes(N, d, P, G_total)
+    if nb == 0:
+        raise nat.NativeError("abc_kde_panels", nat.ABC_ERR_UNSUPPORTED,
+                              f"shape N={N} d={d} P={P} G_total={G_total} beyond the caps")
+    cd = as_dev(coords, device=X.device)
+    out = torch.empty(G_total, dtype=F64, device=X.device)
+    ws = workspace(nb, "kde")
+    nat.call("abc_kde_panels", p(X), p(w), N, d,
+             ctypes.cast(panels, ctypes.c_void_p), P, p(cd), coords.size, p(out),
+             G_total, p(ws), ws.numel(), stream_ptr())
+    return out
+
+
 # ---- proposal / prior / simulator / distance / acceptance ----------------
 
 def cdf_guide(cdf):
